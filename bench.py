@@ -1,6 +1,12 @@
 """Throughput bench: Battle 64x64, 256 agents -- agent-steps/s of the hot path (env.step + obs).
 
-    python bench.py [--gpus N --steps K --warmup W] [--envs E | --total-envs T] [--no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W] [--envs E | --total-envs T] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given (dump_outputs) and
+prints the result line.  --full adds, after the clock, everything else the line can carry: the self-check below
+("check"), the measured write ceiling (roofline.measured_peak, frac_measured), the CPU baseline ("cpu_baseline";
+--no-cpu-baseline leaves it out), and for --policy qnet / mfac the serialised per-phase timing (roofline.kernel_ms,
+env_step_ms, achieved); without --full those fields are null or absent.
 
 Episodes are staggered over envs and the batch is run for one episode cap (400 steps) before
 the warmup, so any K-step window sees the steady mix of episode phases (not just the opening
@@ -21,7 +27,7 @@ touches the GPU) and exits with their status.  --envs E: E envs per rank (weak s
 --total-envs T: T envs split over the ranks (strong scaling, configs[3]: 64 envs over 8 GPUs).
 The only collective is the RCCL all-reduce of the episode statistics.
 
-Self-check (after the clock, outside the timed region): every rank replays --check-envs sampled envs of
+Self-check (--full; after the clock, outside the timed region): every rank replays --check-envs sampled envs of
 its own batch on the C oracle from rollout_init on (tests/rollout_check.py: the oracle steps with a host
 restatement of the device's counter-hash rush policy) and compares the last step's observation, actions,
 rewards and mean action, the state after it (ids, positions, hp), and the env's counters (agent-steps,
@@ -103,7 +109,14 @@ def parse(argv=None):
     # few-env stepper the whole timed region as one launch (8 envs: 0.0356 ms per step at 20, 0.0285 at 64).
     ap.add_argument("--substeps", type=int, default=0,
                     help="consecutive steps of every env per launch (default 0: the engine's choice, 20 at the default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the clock also run what a plain run leaves out: the oracle self-check (--check-envs), "
+                         "the measured write ceiling, the CPU baseline, and (qnet / mfac) the serialised per-phase timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left in the rollout buffers of "
+                         "--dump-envs sampled envs, and every env's counters, as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--dump-envs", type=int, default=8, help="envs per rank sampled by --dump-outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-procs", type=int, default=None,
@@ -129,6 +142,8 @@ def parse(argv=None):
     ap.add_argument("--check-envs", type=int, default=8,
                     help="envs per rank replayed on the C oracle after the timed region (0: no check)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.envs is None and a.total_envs is None and a.policy != "rush":
         a.envs = 8192                 # the network forward bounds these modes (1.2 / 3.4 MFLOP per agent-step)
     if a.split is None and a.policy != "rush":
@@ -390,6 +405,62 @@ def run_check(engs, args, sizes, placement, seeds, world):
             "seconds": time.perf_counter() - t, "mismatches": bad[:16]}
 
 
+# ----------------------------------------------------------------------------- output dump
+def dump_outputs(out_dir, engs, sizes, rows, n_envs, rank=0, world=1):
+    """--dump-outputs: what the last timed step left for a caller of the rollout, as out_dir/<name>.npy (float32 for
+    the engine's float32 buffers, float64 for its integers and doubles), so that two builds run with the same
+    arguments can be compared array for array.  Called after the clock, before anything overwrites the buffers.
+
+    Of n_envs envs spread over the batch (rollout_check.sample_envs; `envs`: their indices): the observation the
+    step acted on (view_g*, feature_g*), its actions, rewards and mean action, and the state after it (ids_g*,
+    pos_g*, hp_g*).  Per-agent arrays keep `rows` rows, the agents of one placement: the engine never writes the rows
+    above; rows past a group's live count hold what an earlier step wrote there (observation, actions, rewards),
+    or zero (ids, pos, hp: the getters leave them unwritten).  Of every env: agent_steps, stats, episode_return,
+    group_num.  With several ranks each writes <name>_rank<r>.npy."""
+    import numpy as np
+    import rollout_check as rc
+    os.makedirs(out_dir, exist_ok=True)
+    recs, picked, base = [], [], 0
+    H = len(engs)
+    G = len(engs[0].handles)
+    # the sampled envs' arrays within 48 MB (a 256x256 env's observation is 20 MB), the counters take the rest
+    per_env = 4 * rows * sum(int(np.prod(engs[0].env.get_view_space(h))) + engs[0].env.get_feature_space(h)[0] + 6
+                             for h in engs[0].handles)
+    n_envs = max(1, min(n_envs, (48 << 20) // per_env))
+    for h, (eng, E) in enumerate(zip(engs, sizes)):
+        envs = rc.sample_envs(E, max(1, n_envs // H + (1 if h < n_envs % H else 0)))
+        recs.append(rc.device_records(eng, envs))
+        picked += [base + e for e in envs]
+        base += E
+    out = {"envs": np.array(picked, dtype=np.float64)}
+    live = np.concatenate([r["group_num"] for r in recs])                        # [k][G], after the step
+    for g in range(G):
+        keep = (np.arange(rows)[None, :] < live[:, g, None])[:, :, None]
+        out["view_g%d" % g] = np.concatenate([r["view"][g][:, :rows] for r in recs])
+        out["feature_g%d" % g] = np.concatenate([r["feature"][g][:, :rows] for r in recs])
+        for name in ("ids", "pos", "hp"):
+            out["%s_g%d" % (name, g)] = np.where(keep, np.concatenate([r[name][g][:, :rows] for r in recs]), 0)
+    out["actions"] = np.concatenate([r["actions"][:, :, :rows] for r in recs])
+    out["rewards"] = np.concatenate([r["rewards"][:, :, :rows] for r in recs])
+    out["mean_action"] = np.concatenate([r["mean"] for r in recs])
+    # every env's counters
+    import torch
+    whole = {"agent_steps": (1, torch.int64), "stats": (4, torch.float64), "episode_return": (G, torch.float32),
+             "group_num": (G, torch.int32)}
+    for name, (w, dt) in whole.items():
+        parts = []
+        for eng, E in zip(engs, sizes):
+            buf = torch.empty((E, w), dtype=dt, device="cuda")
+            eng.rollout_copy(name, buf)
+            eng.sync()
+            parts.append(buf.cpu().numpy())
+        out[name] = np.concatenate(parts)
+    tag = "_rank%d" % rank if world > 1 else ""
+    for name, a in out.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(out_dir, name + tag + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------- learned policy
 QNET_FLOP_PER_AGENT = 2 * (121 * 32 * 63 + 81 * 32 * 288 + 2592 * 256 + 34 * 32 + 21 * 64 + 64 * 32 + 320 * 128 +
                            128 * 64 + 64 * 21)          # 3,417,920: the mean-field QNet forward of one agent
@@ -482,8 +553,12 @@ def main_qnet(args):
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     units = float((agent_steps() - a0).item())
-    # the phases, serialised: every engine on the main stream, events around each engine's forwards and step
-    n_ph = max(1, min(args.steps, 6))
+    for eng in engs:
+        eng.rollout_check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engs, sizes, max(len(left), len(right)), args.dump_envs)
+    # --full: the phases, serialised: every engine on the main stream, events around each engine's forwards and step
+    n_ph = max(1, min(args.steps, 6)) if args.full else 0
     evs = []
     for h, eng in enumerate(engs):
         eng.set_stream(main)
@@ -498,8 +573,8 @@ def main_qnet(args):
             evs.append(e)
         step_no[0] += 1
     torch.cuda.synchronize()
-    fwd_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / n_ph
-    env_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / n_ph
+    fwd_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / n_ph if n_ph else None
+    env_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / n_ph if n_ph else None
     for eng in engs:
         eng.rollout_check()
     units_step = units / args.steps
@@ -510,6 +585,7 @@ def main_qnet(args):
     else:
         flop_dense = flop_per_agent = QNET_FLOP_PER_AGENT
     flops = flop_per_agent * units_step
+    achieved = flops / (fwd_ms * 1e-3) / 1e12 if n_ph else None          # (null without --full: no phase timing)
     what = ("learned MFAC policy (HIP actor-critic forward + draw)" if ac else
             "learned MF-Q policy (HIP QNet forward)")
     line = {"metric": "agent-steps/sec (env.step+obs) Battle %dx%dx%d agents, %s" % (args.map, args.map, args.agents,
@@ -522,13 +598,14 @@ def main_qnet(args):
                                       "; the envs as %d engines on %d HIP streams" % (H, H) if H > 1 else ""),
                        "envs_per_gpu": E, "policy": args.policy, "engines": H,
                        "view_inputs": (pols[0].input_support_size() or 1183) if ac else 1183},
-            "roofline": {"bound": "mfma", "achieved": flops / (fwd_ms * 1e-3) / 1e12, "peak": F32_MFMA_PEAK_TFS,
-                         "unit": "TFLOP/s", "frac": flops / (fwd_ms * 1e-3) / 1e12 / F32_MFMA_PEAK_TFS,
+            "roofline": {"bound": "mfma", "achieved": achieved, "peak": F32_MFMA_PEAK_TFS,
+                         "unit": "TFLOP/s", "frac": achieved / F32_MFMA_PEAK_TFS if n_ph else None,
                          "traffic": None, "kernel": "k_acnet (x2 groups)" if ac else "k_qnet_conv + k_qnet_head (x2 groups)",
                          "kernel_ms": fwd_ms, "env_step_ms": env_ms,
-                         "kernel_ms_is": "the forwards (both groups, every engine) of one step, serialised after the "
-                                         "clock on one stream (HIP events; mean of %d steps); env_step_ms: the k_rollout "
-                                         "step + observation of every engine the same way" % n_ph,
+                         "kernel_ms_is": ("the forwards (both groups, every engine) of one step, serialised after the "
+                                          "clock on one stream (HIP events; mean of %d steps); env_step_ms: the k_rollout "
+                                          "step + observation of every engine the same way" % n_ph) if n_ph else
+                                         "null: the serialised phases are timed with --full",
                          "flop_per_unit": flop_per_agent, "flop_per_unit_dense": flop_dense,
                          "flop_is": "the MFMA FLOPs executed per agent (the view layer over the inputs the "
                                     "observation can make non-zero when view_inputs < 1183); flop_per_unit_dense: the "
@@ -670,9 +747,15 @@ def main():
     kernel_ms = sum(a.elapsed_time(b) for a, b in segs) / len(chunks)
     local_units = float((a1 - a0).item())
     elapsed, total_units = reduce_timing(t1 - t0, local_units, "cuda")
-    check = run_check(engs, args, sizes, [left, right], seeds, world)
-    # the measured write ceiling of this GPU (after the check: it overwrites the view buffer)
-    ceiling = measure_ceiling(eng, BYTES_PER_AGENT_STEP * local_units / len(chunks)) if args.ceiling else None
+    for e in engs:
+        e.rollout_check()                    # the device and queue error words: a set one raises
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engs, sizes, max(len(left), len(right)), args.dump_envs, rank, world)
+    # --full only, after the clock: the oracle self-check, then the measured write ceiling of this GPU (after the
+    # check and the dump: it overwrites the view buffer)
+    check = run_check(engs, args, sizes, [left, right], seeds, world) if args.full else None
+    ceiling = (measure_ceiling(eng, BYTES_PER_AGENT_STEP * local_units / len(chunks))
+               if args.full and args.ceiling else None)
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         steps_per_timed_launch = args.steps / len(chunks)       # the mean launch kernel_ms is
@@ -748,7 +831,7 @@ def main():
         }
         if check is not None:
             line["check"] = check
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = run_cpu_baseline(args.cpu_seconds, args.map, args.agents, args.cpu_procs)
         print(json.dumps(line), flush=True)
     if world > 1:
