@@ -142,12 +142,22 @@ int mfx_battle_rollout_path(void *game, int *path);
 /* Lanes over which the rollout sums a group's rewards of an env with n_agents agents: the summation order of
  * the episode returns (64: one wave, 256 / 512: a workgroup's lane-strided partials, then wave sums). */
 int mfx_battle_rollout_sum_lanes(void *game, int n_agents, int *lanes);
-/* A learned policy in the loop (the fused k_rollout path: batches of LDS-sized envs larger than the few-env
- * threshold): mode 2 writes every env's observation into the rollout buffers; mode 1 takes the actions in
- * the rollout's action buffer (a policy forward on that observation, e.g. mfx_qnet_act_rollout), runs
- * set_action / step / reward / mean action / clear_dead / restart and writes the next observation.  The
- * mean-action buffer then holds each group's former_act_prob (zeros at an episode's first step). */
+/* A learned policy in the loop: mode 2 writes every env's observation into the rollout buffers; mode 1 takes
+ * the actions in the rollout's action buffer (a policy forward on that observation, e.g. mfx_qnet_act_rollout;
+ * an id outside [0, 64) is rejected like set_action's and left out of the mean action), runs set_action / step /
+ * reward / mean action / clear_dead / restart and writes the next observation.  The mean-action buffer then
+ * holds each group's former_act_prob (zeros at an episode's first step).  Every plan but the observation/step
+ * pipeline (MFX_ROLLOUT_PIPE=1) takes it: large batches of LDS-sized envs on the fused k_rollout, large envs and
+ * batches of few LDS-sized envs on k_rollout_big + k_observe_items, one step per call on the engine's stream
+ * (mfx_battle_rollout_policy_path).  A mode-2 call must precede the first mode-1 call after rollout_init,
+ * rollout_step or any per-call API use; rollout_step and the policy steps interleave exactly. */
 int mfx_battle_rollout_policy_step(void *game, int mode);
+/* The kernels rollout_policy_step runs, numbered like mfx_battle_rollout_path: 0 k_rollout, 2 k_observe_items +
+ * k_rollout_big; -1 when the plan refuses a learned policy. */
+int mfx_battle_rollout_policy_path(void *game, int *path);
+/* Copy `bytes` bytes from src (device or host) into a rollout buffer, async on the engine stream: the inverse of
+ * mfx_battle_rollout_copy.  Only "actions" is writable. */
+int mfx_battle_rollout_write(void *game, const char *name, int group, const void *src, size_t bytes);
 /* The inputs of group `group`'s observation view that can be non-zero (Map.cc:130-218): mask[n] (n = view_h *
  * view_w * n_ch, NHWC) = 1 for every channel of a cell inside the view range and for the minimap channels of the
  * cells outside it, else 0 (never written: always zero). */

@@ -313,6 +313,11 @@ __device__ __forceinline__ void big_env_copy(const State& s, int G, const EnvVie
 // kStepStore -- write it back to HBM at the end; kStepPrep -- the next observation's shared inputs (obs_prep_env).
 // The queue kernel's step passes all three; the pipelined stepper keeps the env in LDS between its steps.
 constexpr int kStepLoad = 1, kStepStore = 2, kStepPrep = 4, kStepAll = 7;
+// kExt: the actions come from ra.actions (a learned policy's forward wrote them) instead of the on-device rush
+// policy, as in agent_phase: nothing is written to ra.actions, an id outside [0, 64) stays out of the mean action
+// (set_action rejects it), and an episode end zeroes the env's mean-action rows (the next episode's first
+// former_act_prob, k_rollout kMode 1).
+template <bool kExt = false>
 __device__ __forceinline__ void big_env_step(const GameParams& gp, const State& s, const RolloutArgs& ra, int e,
                                              uint32_t step_index, char* smem, int* misc, int flags = kStepAll) {
     // misc: 0 n_atk, 1 n_mov, 2 episode end
@@ -383,6 +388,14 @@ __device__ __forceinline__ void big_env_step(const GameParams& gp, const State& 
     }
     for (int i = TID; i < G * 64; i += blockDim.x) ahist[i] = 0;
     __syncthreads();
+    if constexpr (kExt) {
+        for (int t = TID; t < ntot; t += blockDim.x) {
+            int g = 0, i = t;
+            while (i >= v.grp_n[g]) { i -= v.grp_n[g]; ++g; }
+            const int a = ra.actions[((size_t)e * G + g) * ra.rowcap + i];
+            if ((unsigned)a < 64u) atomicAdd(&ahist[g * 64 + a], 1);
+        }
+    } else {
     const uint32_t ekey = ra.policy_seed ^ mix32(step_index * 0x9E3779B9u + (uint32_t)(ra.env_base + e) * 0x632BE5ABu);
     // two agents per lane per pass: both policies' HBM loads (position, 8 attack cells, their
     // occupants) are in flight together, the stores come after
@@ -405,6 +418,7 @@ __device__ __forceinline__ void big_env_step(const GameParams& gp, const State& 
             ra.actions[((size_t)e * G + gg[j]) * ra.rowcap + ii[j]] = a[j];
             atomicAdd(&ahist[gg[j] * 64 + a[j]], 1);
         }
+    }
     }
     __syncthreads();
     for (int t = TID; t < G * 64; t += blockDim.x) {
@@ -481,6 +495,9 @@ __device__ __forceinline__ void big_env_step(const GameParams& gp, const State& 
             for (int i = TID; i < img_scal[g]; i += blockDim.x) v.grp_ids[g * cap + i] = im.grp_ids[g * cap + i];
         if (TID < G) { v.grp_n[TID] = img_scal[TID]; v.grp_dead[TID] = 0; v.grp_reward[TID] = 0.0f; }
         if (TID == 0) { s.id_counter[e] = idc; s.rid_off[e] = 0; }
+        if constexpr (kExt)
+            for (int t = TID; t < G * ra.mean_stride; t += blockDim.x)
+                ra.mean_act[(size_t)e * G * ra.mean_stride + t] = 0.0;
         __syncthreads();
     }
     MFX_BSTAMP(bs.srow, 13);
@@ -519,13 +536,15 @@ __device__ __attribute__((noinline)) void big_env_step_call(const GameParams& gp
     big_env_step(gp, s, ra, e, step_index, smem, misc);
 }
 
+// kExt: a learned policy's step (big_env_step<true>: the actions are read from ra.actions).
+template <bool kExt>
 __global__ void __launch_bounds__(kBigRolloutThreads) k_rollout_big(const GameParams* __restrict__ gpp,
                                                              const RolloutCtx* __restrict__ ctx, uint32_t step_index) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int misc[4];
     const RolloutArgs& ra = ctx->ra;
     const int e = blockIdx.x;
-    big_env_step(*gpp, ctx->s, ra, e, step_index, smem, misc);
+    big_env_step<kExt>(*gpp, ctx->s, ra, e, step_index, smem, misc);
     if (ra.obs_mm && ra.obs_items) {
         __syncthreads();
         obs_file_items(ra, global_view(ctx->s, e, gpp->n_groups), gpp->n_groups, e, (int)((step_index + 1) & 1));

@@ -275,6 +275,15 @@ public:
     DevBuf<RolloutCtx> ro_qc_ctx;
     static uint32_t qtag(uint32_t launch) { return launch % 63u + 1u; }   // 6 tag bits (rollout_big.inc), never 0
     bool ro_prep_stale = true;               // ro_mm / ro_info / items lag the state (per-call calls since)
+    // A learned policy on the large-env plans (rollout_policy_step): all E envs as one batch on the engine's own
+    // stream, k_observe_items (lists of kItemRows agents in ro_items / ro_cnt) + k_rollout_big<ext>.  Its args are its
+    // own: with ro_bigq, ra holds the queue kernel's rows per item and ro_sub_ra is cut from that.
+    RolloutArgs ro_pol_ra{};
+    DevBuf<RolloutCtx> ro_pol_ctx;
+    int ro_pol_item_grid = 0;                // its k_observe_items grid: the launch has the chip to itself
+    // whose observation inputs, item lists and parities are current: 0 rollout_step's form, 1 the policy form's.
+    // The other form re-seeds on its next call, as after per-call calls (ro_prep_stale).
+    int ro_prep_form = 0;
     DevBuf<int32_t> ro_actions, ro_eplen, ro_tx, ro_ty;
     DevBuf<double> ro_mean, ro_stats;
     DevBuf<unsigned long long> ro_steps;
@@ -1298,6 +1307,15 @@ public:
                     ra.obs_items = ro_items.p; ra.obs_cnt = ro_cnt.p;
                     ra.obs_par_stride = par_stride; ra.obs_item_rows = R;
                     MFX_HIP_THROW(observe_items_grid(gp, R, &ro_item_grid));
+                    {   // the policy form's launch runs alone: every slot of the chip (256x256, 2048 envs: 7.9 ms per
+                        // step + observation against 11.6 at a third), but no more workgroups than items (one
+                        // 40x40 env: 0.13 ms against 0.35 with the full grid) -- MFX_POLICY_ITEM_DIV: A/B only
+                        const char* pd = getenv("MFX_POLICY_ITEM_DIV");
+                        const long long items = (long long)E * n_groups() * (long long)slots;
+                        ro_pol_item_grid = std::max(1, ro_item_grid / (pd && atoi(pd) > 0 ? atoi(pd) : 1));
+                        ro_pol_item_grid = (int)std::min<long long>(ro_pol_item_grid, std::max<long long>(kXcds, items));
+                        if (ro_pol_item_grid >= kXcds) ro_pol_item_grid -= ro_pol_item_grid % kXcds;
+                    }
                     ro_item_grid = std::max(1, ro_item_grid / kItemGridDiv);
                     if (ro_item_grid >= kXcds) ro_item_grid -= ro_item_grid % kXcds;   // as many per XCD
                     // the queue-driven kernel: item words hold 13 env bits and 6 chunk bits
@@ -1389,6 +1407,21 @@ public:
                 for (auto& x : ro_ev) if (!x) MFX_HIP_THROW(hipEventCreateWithFlags(&x, hipEventDisableTiming));
                 MFX_HIP_THROW(hipMemcpyAsync(ro_sub_ctx.p, subs.data(), sizeof(RolloutCtx) * K, hipMemcpyHostToDevice,
                                              stream));
+                {   // the policy form: one batch, the item lists of kItemRows agents (never the queue kernel's Rq)
+                    RolloutArgs q = ra;
+                    q.env_base = 0;
+                    q.few_pipe = 0;
+                    if (q.obs_items) {
+                        const size_t slots = (size_t)n_groups() * ((ra.rowcap + kItemRows - 1) / kItemRows);
+                        q.obs_item_rows = kItemRows;
+                        q.obs_list_stride = (size_t)((E + q.obs_lists - 1) / q.obs_lists) * slots;
+                    }
+                    ro_pol_ra = q;
+                    RolloutCtx pc{};
+                    pc.s = s; pc.ra = q; pc.w = s;
+                    ro_pol_ctx.ensure(1);
+                    MFX_HIP_THROW(hipMemcpy(ro_pol_ctx.p, &pc, sizeof(RolloutCtx), hipMemcpyHostToDevice));
+                }
             } else {
                 const char* pv = getenv("MFX_ROLLOUT_PIPE");
                 ro_pipe = pv ? atoi(pv) != 0 : kPipeDefault;
@@ -1442,6 +1475,9 @@ public:
             const State& planned = ro_pipe ? ro_pipe_host[ro_par].s : ro_ctx_host.s;
             if (s.cap != ro_cap || memcmp(&planned, &s, sizeof(State)) != 0) MFX_CHECK(rollout_plan());
         }
+        // after a learned policy's launches the queue kernel's filings, tags and parities (and the pipeline's item
+        // lists) are out of date: re-seed
+        if (ro_prep_form != 0) { ro_prep_stale = true; ro_prep_form = 0; }
         if (ro_big && ro_bigq && ra.few_pipe) {
             // the pipelined few-env form: every launch files and observes its own items (parity 0, a fresh tag),
             // the steppers claimed per XCD; q_left must read 0 (no items outstanding) at a launch start
@@ -1590,7 +1626,9 @@ public:
 
     // A learned policy's launches (include/magent_amd.h mfx_battle_rollout_policy_step): mode 2 observes every
     // env into the rollout buffers; mode 1 acts with the actions in the rollout's action buffer (the
-    // policy's forward on that observation), steps, and observes the new state.  The fused k_rollout only.
+    // policy's forward on that observation), steps, and observes the new state.  LDS-sized envs in large batches:
+    // the fused k_rollout (kMode).  Every large-env plan (ro_big: large envs, few LDS-sized envs, pipelined or not,
+    // MFX_BIG_FUSED=0): k_rollout_big<ext> + k_observe_items on the engine's stream (rollout_policy_big).
     int rollout_policy_step(int mode) {
         MFX_CHECK(flush_deferred());
         touch();
@@ -1601,9 +1639,10 @@ public:
             const State& planned = ro_pipe ? ro_pipe_host[ro_par].s : ro_ctx_host.s;
             if (s.cap != ro_cap || memcmp(&planned, &s, sizeof(State)) != 0) MFX_CHECK(rollout_plan());
         }
-        if (ro_big || ro_pipe)
-            return fail("rollout_policy_step: a learned policy steps on the fused k_rollout (LDS-sized envs; batches of "
-                        "more than %d envs or MFX_SMALL_E=0; MFX_ROLLOUT_PIPE=0)", small_e_max());
+        if (ro_big) return rollout_policy_big(mode);
+        if (ro_pipe)
+            return fail("rollout_policy_step: a learned policy does not step on the observation/step pipeline "
+                        "(MFX_ROLLOUT_PIPE=1); unset it");
         MFX_HIP(launch_rollout_mode(gp, d_gp, s, ro_ctx.p, ra.rowcap, ra.step_index, ra.work_sel, (int)(ro_launch % 6),
                                     ro_grid, mode, stream));
         ro_launch++;
@@ -1611,6 +1650,50 @@ public:
         ra.work_sel ^= 1;
         cells_stale = true;
         return 0;
+    }
+
+    // The policy form of the large-env plans.  The observation of step t reads the item lists of parity t & 1:
+    // mode 2 files them itself (k_obs_prep, after clearing both parities' counters: a drained list's tickets are
+    // spent, and after a rollout_step the lists hold the other form's items); mode 1's k_rollout_big<ext> files
+    // parity (t + 1) & 1 for the observation that follows it, whose workgroup 0 clears parity t & 1 for the step
+    // after.  Everything runs on the engine's stream, in order.
+    int rollout_policy_big(int mode) {
+        MFX_CHECK(sync_cells());
+        const bool items = ro_pol_ra.obs_items != nullptr;
+        auto observe = [&](int par) -> int {
+            if (items) {
+                MFX_HIP(launch_observe_items(gp, d_gp, s, ro_pol_ra, par, ro_pol_item_grid, stream));
+            } else {                                   // generic (non-Battle-shape) observation
+                for (int g = 0; g < n_groups(); g++)
+                    MFX_HIP(launch_observe(gp, d_gp, s, g, ro_pol_ra.rowcap, ro_pol_ra.view[g], ro_pol_ra.feat[g],
+                                           ro_pol_ra.rowcap, stream));
+            }
+            return 0;
+        };
+        if (mode == 2) {
+            if (items) {
+                MFX_HIP(hipMemsetAsync(ro_cnt.p, 0, sizeof(int32_t) * ro_cnt.n, stream));
+                MFX_HIP(launch_obs_prep(d_gp, s, ro_pol_ra, (int)(ra.step_index & 1), stream));
+            }
+            MFX_CHECK(observe((int)(ra.step_index & 1)));
+        } else {
+            if (ro_prep_stale || ro_prep_form != 1)
+                return fail("rollout_policy_step: observe first (mode 2) after rollout_init, rollout_step or a per-call "
+                            "call: the action buffer must follow the current observation");
+            MFX_HIP(launch_rollout_big(gp, d_gp, s, ro_pol_ctx.p, ra.step_index, ra.lds_step, stream, true));
+            ra.step_index++;
+            MFX_CHECK(observe((int)(ra.step_index & 1)));
+        }
+        ro_launch++;
+        ro_prep_stale = false;
+        ro_prep_form = 1;
+        return 0;
+    }
+
+    // Which kernels rollout_policy_step runs (include/magent_amd.h mfx_battle_rollout_policy_path).
+    int rollout_policy_path() const {
+        if (!rollout_ready || (!ro_big && ro_pipe)) return -1;
+        return ro_big ? 2 : 0;
     }
 
     // Synchronise and report the device error word and, on the queue-driven large-env kernel, its queue
@@ -2548,6 +2631,17 @@ MFX_API int mfx_battle_rollout_copy_at(void* game, const char* name, int group, 
     MFX_HIP(hipMemcpyAsync(dst, static_cast<const char*>(src) + offset, bytes, hipMemcpyDefault, e->stream));
     return 0;
 }
+// The inverse, for the buffers a caller supplies: "actions" (a policy's actions for mfx_battle_rollout_policy_step).
+MFX_API int mfx_battle_rollout_write(void* game, const char* name, int group, const void* src, size_t bytes) {
+    BattleEngine* e = MFX_ENV(game);
+    if (strcmp(name, "actions") != 0) return mfx::fail("rollout_write: buffer %s is not writable (only actions)", name);
+    void* dst = nullptr;
+    size_t n = 0;
+    MFX_CHECK(e->rollout_buffer(name, group, &dst, &n));
+    if (bytes > n) return mfx::fail("rollout_write: %zu bytes given, buffer has %zu", bytes, n);
+    MFX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, e->stream));
+    return 0;
+}
 // Diagnostic build only: route k_rollout phase stamps ([E][16] u64 s_memtime) to d_buf.
 MFX_API int mfx_battle_set_stamp_buffer(void* d_buf) {
     MFX_HIP(mfx::set_stamp_buffer((unsigned long long*)d_buf));
@@ -2566,6 +2660,13 @@ MFX_API int mfx_battle_rollout_check(void* game) {
 // A learned policy's launches: mode 2 observes every env, mode 1 acts with the action buffer, steps, observes.
 MFX_API int mfx_battle_rollout_policy_step(void* game, int mode) {
     MFX_GUARD(MFX_ENV(game)->rollout_policy_step(mode));
+}
+// The kernels rollout_policy_step runs, numbered like mfx_battle_rollout_path: 0 k_rollout, 2 k_observe_items +
+// k_rollout_big; -1: the plan refuses a learned policy (MFX_ROLLOUT_PIPE=1).
+MFX_API int mfx_battle_rollout_policy_path(void* game, int* path) {
+    if (!MFX_ENV(game)->rollout_ready) return mfx::fail("rollout_policy_path before rollout_init");
+    *path = MFX_ENV(game)->rollout_policy_path();
+    return 0;
 }
 // The kernels rollout_step runs: 0 k_rollout, 1 k_rollout_obs + k_rollout (pipeline), 2 k_observe_items +
 // k_rollout_big (large-env pipeline), 3 k_rollout_bigq.

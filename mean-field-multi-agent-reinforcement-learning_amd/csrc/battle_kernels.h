@@ -42,8 +42,9 @@ hipError_t launch_rollout_obs(const GameParams& gp, const GameParams* d_gp, cons
                               int rows, int work_sel, int qphase, int grid, hipStream_t st);
 hipError_t rollout_obs_grid(const GameParams& gp, const State& s, int rows, int per_cu_want, int* grid);
 size_t big_step_smem_bytes(const GameParams& gp, int cap, int acap, bool rollout, bool lds_env = false);
+// ext: a learned policy's step (the actions are read from RolloutArgs::actions, k_rollout_big<true>)
 hipError_t launch_rollout_big(const GameParams& gp, const GameParams* d_gp, const State& s, const RolloutCtx* d_ctx,
-                              uint32_t step_index, bool lds_env, hipStream_t st);
+                              uint32_t step_index, bool lds_env, hipStream_t st, bool ext = false);
 hipError_t rollout_grid(const GameParams& gp, const State& s, int rows, int split, int per_cu_want, int* grid);
 // large envs, one queue-driven launch per n_sub steps (k_rollout_bigq)
 // lds_env: the few-env path stages each env in LDS for its step (RolloutArgs::lds_step)

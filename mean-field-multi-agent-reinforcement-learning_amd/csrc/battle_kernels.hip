@@ -305,10 +305,11 @@ hipError_t launch_step(const GameParams& gp, const GameParams* d_gp, const State
 }
 
 hipError_t launch_rollout_big(const GameParams& gp, const GameParams* d_gp, const State& s, const RolloutCtx* d_ctx,
-                              uint32_t step_index, bool lds_env, hipStream_t st) {
+                              uint32_t step_index, bool lds_env, hipStream_t st, bool ext) {
     const size_t smem = big_step_smem_bytes(gp, s.cap, s.acap, true, lds_env);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-    k_rollout_big<<<s.E, kBigRolloutThreads, smem, st>>>(d_gp, d_ctx, step_index);
+    if (ext) k_rollout_big<true><<<s.E, kBigRolloutThreads, smem, st>>>(d_gp, d_ctx, step_index);
+    else k_rollout_big<false><<<s.E, kBigRolloutThreads, smem, st>>>(d_gp, d_ctx, step_index);
     return hipGetLastError();
 }
 

@@ -34,7 +34,7 @@ class BattleBatch:
                    "mfx_battle_rollout_info", "mfx_battle_group_capacity", "mfx_battle_rollout_set_substeps",
                    "mfx_battle_rollout_copy_at", "mfx_battle_rollout_check", "mfx_battle_rollout_path",
                    "mfx_battle_rollout_policy_step", "mfx_battle_rollout_sum_lanes", "mfx_battle_rollout_mean_stride",
-                   "mfx_battle_rollout_get_substeps"):
+                   "mfx_battle_rollout_get_substeps", "mfx_battle_rollout_policy_path", "mfx_battle_rollout_write"):
             try:
                 getattr(self._dll, fn).restype = ctypes.c_int
             except AttributeError:          # an older build of the library (A/B runs)
@@ -158,13 +158,29 @@ class BattleBatch:
         self._check(self._dll.mfx_battle_rollout_step(self.game, n_steps), "rollout_step")
 
     # ------------------------------------------------------------------ learned policy in the loop
+    # Every plan takes a learned policy except the observation/step pipeline (MFX_ROLLOUT_PIPE=1): large batches
+    # of LDS-sized envs step on the fused k_rollout; large envs (256x256 / 4096 agents) and batches of few
+    # LDS-sized envs (down to one env) on k_rollout_big + k_observe_items, one step per call on the engine's
+    # stream (rollout_policy_path).  rollout_step and the policy steps interleave exactly.
+    def rollout_policy_path(self):
+        """Name of the kernels rollout_policy_step runs ("k_rollout" or "k_observe_items+k_rollout_big"); None
+        when the plan refuses a learned policy (MFX_ROLLOUT_PIPE=1)."""
+        p = ctypes.c_int()
+        self._check(self._dll.mfx_battle_rollout_policy_path(self.game, ctypes.byref(p)), "rollout_policy_path")
+        return self.PATHS[p.value] if p.value >= 0 else None
+
     def rollout_policy_observe(self):
-        """Write every env's observation into the rollout buffers (the first step of a learned-policy loop)."""
+        """Write every env's observation into the rollout buffers: the first call of a learned-policy loop, and
+        needed again before the next rollout_policy_step after rollout_init, rollout_step or any per-call API
+        use (the action buffer must follow the current observation).  Supported on every plan but
+        MFX_ROLLOUT_PIPE=1 (rollout_policy_path)."""
         self._check(self._dll.mfx_battle_rollout_policy_step(self.game, 2), "rollout_policy_step")
 
     def rollout_policy_step(self):
         """Act with the rollout's action buffer (a policy's forward on the current observation, e.g.
-        mfrl_amd.policy.QNetHIP.act_rollout), step every env, observe the new state."""
+        mfrl_amd.policy.QNetHIP.act_rollout, or any actions written with rollout_write), step every env, observe
+        the new state.  Supported on every plan but MFX_ROLLOUT_PIPE=1 (rollout_policy_path); a
+        rollout_policy_observe call must come first after rollout_init, rollout_step or any per-call API use."""
         self._check(self._dll.mfx_battle_rollout_policy_step(self.game, 1), "rollout_policy_step")
 
     def mean_stride(self):
@@ -209,6 +225,19 @@ class BattleBatch:
                                                   else dst.nbytes)
         self._check(self._dll.mfx_battle_rollout_copy(self.game, name.encode(), group, ctypes.c_void_p(ptr),
                                                       ctypes.c_size_t(size)), "rollout_copy")
+
+    WRITABLE = ("actions",)
+
+    def rollout_write(self, name, src, group=0):
+        """Copy src (torch tensor or numpy array, device or host) into a device rollout buffer on the engine's
+        stream: the inverse of rollout_copy.  Only "actions" ([E][G][rowcap] int32, the buffer
+        rollout_policy_step acts with) is writable."""
+        if name not in self.WRITABLE:
+            raise ValueError("rollout_write: buffer %r is not writable (only %s)" % (name, ", ".join(self.WRITABLE)))
+        ptr = src.data_ptr() if hasattr(src, "data_ptr") else src.ctypes.data
+        size = src.numel() * src.element_size() if hasattr(src, "numel") else src.nbytes
+        self._check(self._dll.mfx_battle_rollout_write(self.game, name.encode(), group, ctypes.c_void_p(ptr),
+                                                       ctypes.c_size_t(size)), "rollout_write")
 
     def rollout_copy_at(self, name, dst, offset, group=0, nbytes=None):
         """Copy bytes [offset, offset + nbytes) of a device rollout buffer into dst."""

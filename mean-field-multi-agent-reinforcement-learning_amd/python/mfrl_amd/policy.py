@@ -144,7 +144,12 @@ class QNetHIP:
 
     def act_rollout(self, eng, group):
         """Actions of group `group` of a BattleBatch rollout from its current observation buffers and
-        former mean actions, written into the rollout's action buffer [E][G][rowcap] (live rows only)."""
+        former mean actions, written into the rollout's action buffer [E][G][rowcap] (live rows only).
+
+        Works on every plan that takes a learned policy (BattleBatch.rollout_policy_path: all but
+        MFX_ROLLOUT_PIPE=1 -- large batches, large envs and few-env batches alike; E, rowcap and the buffers come
+        from the engine).  The observation must be current: call eng.rollout_policy_observe() after rollout_init,
+        rollout_step or any per-call API use, before the first act_rollout / rollout_policy_step pair."""
         E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
         if self._rows is None or self._rows.numel() < rows_scratch(E, rc):
             self._rows = torch.empty(rows_scratch(E, rc), dtype=torch.int32, device="cuda")
