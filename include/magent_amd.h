@@ -206,6 +206,13 @@ int mfx_qnet_blob_size(int feature, int n_action, int use_mf, size_t *n_floats, 
 int mfx_qnet_create(int view_h, int view_w, int n_ch, int feature, int n_action, int use_mf, void **handle);
 int mfx_qnet_destroy(void *handle);
 int mfx_qnet_set_weights(void *handle, const float *d_blob, size_t n_floats, void *stream);
+/* Acting precision of mfx_qnet_forward / mfx_qnet_act_rollout: 0 = f32 (the default at create), 1 = bf16 matrix
+ * operands (weights, inputs and each layer's activation rounded to nearest even), f32 accumulation, biases, ReLU
+ * and Q values (csrc/qnet_bf16_kernels.hip states the contract).  Any other value is refused and the handle keeps
+ * its mode.  The f32 blob is kept in both modes; with weights set, the images the new mode lacks are built on
+ * `stream`, so switching needs no re-upload and the f32 results are the same before and after. */
+int mfx_qnet_set_precision(void *handle, int precision, void *stream);
+int mfx_qnet_precision(void *handle, int *precision);
 /* n agents: view [n][1183], feature [n][F], prob [n][A] (mean field, else null) -> q [n][A], act [n] */
 int mfx_qnet_forward(void *handle, const float *d_view, const float *d_feat, const float *d_prob, int n, float *d_q,
                      int32_t *d_act, void *stream);

@@ -29,6 +29,7 @@
 
 #include "mfx_common.h"
 #include "policy_gemm.h"
+#include "qnet_bf16.h"
 #include "../../include/magent_amd.h"
 
 namespace mfx {
@@ -453,7 +454,23 @@ struct QNetHandle {
     DevBuf<float> conv;           // [n][2592] activations between the kernels
     float* img = nullptr;         // Dense-Obs's weight image (made by set_weights)
     bool imaged = false;
+    int precision = 0;            // 0: f32 (the kernels above), 1: bf16 operands (qnet_bf16_kernels.hip)
+    QB16Net b16{};
+    uint4* b16_img = nullptr;     // the nine bf16 images, allocated by the first switch to bf16
+    bool b16_imaged = false;      // ... and made from the blob's current weights
 };
+
+// The bf16 images of the blob's current weights (allocated on first use).
+int qnet_b16_images(QNetHandle* q, hipStream_t st) {
+    if (!q->b16_img && hipMalloc(&q->b16_img, qb16_total_units(q->dev.F, q->dev.use_mf) * sizeof(uint4)) != hipSuccess)
+        return fail("qnet: hipMalloc of the bf16 weight images");
+    const QNetDev& d = q->dev;
+    const float* const m[18] = {d.w1, d.b1, d.w2, d.b2, d.wd, d.bd, d.we, d.be, d.wp1, d.bp1, d.wp2, d.bp2, d.w2d, d.b2d,
+                                d.wo, d.bo, d.wq, d.bq};
+    MFX_HIP(qb16_build(&q->b16, m, d.F, d.A, d.use_mf, q->b16_img, st));
+    q->b16_imaged = true;
+    return 0;
+}
 
 // Offsets (floats) of every matrix / bias in the packed blob, in the order of QNetDev.
 void qnet_layout(int F, int A, int use_mf, size_t* off, size_t* total, int* Fp, int* Ap, int* Kc) {
@@ -512,6 +529,7 @@ MFX_API int mfx_qnet_destroy(void* handle) {
     if (!q) return 0;
     if (q->blob) (void)hipFree(q->blob);
     if (q->img) (void)hipFree(q->img);
+    if (q->b16_img) (void)hipFree(q->b16_img);
     delete q;
     return 0;
 }
@@ -523,6 +541,24 @@ MFX_API int mfx_qnet_set_weights(void* handle, const float* d_blob, size_t n_flo
     MFX_HIP(hipMemcpyAsync(q->blob, d_blob, n_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     MFX_HIP(launch_weight_image(q->dev.wd, kQFlat, kQHObs, q->img, (hipStream_t)stream));
     q->imaged = true;
+    q->b16_imaged = false;
+    if (q->precision == 1) MFX_CHECK(qnet_b16_images(q, (hipStream_t)stream));
+    return 0;
+}
+
+// precision 0: f32 (the default), 1: bf16 matrix operands with f32 accumulation (qnet_bf16_kernels.hip's contract).
+// The f32 blob and its image stay, so switching needs no re-upload; with weights set, the images the new mode
+// lacks are built on `stream`.
+MFX_API int mfx_qnet_set_precision(void* handle, int precision, void* stream) {
+    auto* q = static_cast<QNetHandle*>(handle);
+    if (precision != 0 && precision != 1) return fail("qnet_set_precision: %d (0: f32, 1: bf16)", precision);
+    if (precision == 1 && q->imaged && !q->b16_imaged) MFX_CHECK(qnet_b16_images(q, (hipStream_t)stream));
+    q->precision = precision;
+    return 0;
+}
+
+MFX_API int mfx_qnet_precision(void* handle, int* precision) {
+    *precision = static_cast<QNetHandle*>(handle)->precision;
     return 0;
 }
 
@@ -536,7 +572,10 @@ static int qnet_run(QNetHandle* q, const float* view, size_t view_ld, const floa
                     hipStream_t st, const int32_t* d_n = nullptr) {
     if (n <= 0) return 0;
     if (q->dev.use_mf && !prob) return fail("qnet: the mean-field net needs prob");
-    try { q->conv.ensure((size_t)std::min(n, kQPass) * kQFlat); } catch (const HipFailure& f) { return fail("%s", f.what()); }
+    const bool b16 = q->precision == 1;
+    if (b16 && !q->b16_imaged) return fail("qnet: the bf16 forward needs weights (mfx_qnet_set_weights)");
+    // (bf16: the pass buffer holds 2-byte activations, half the floats)
+    try { q->conv.ensure((size_t)std::min(n, kQPass) * (b16 ? kQFlat / 2 : kQFlat)); } catch (const HipFailure& f) { return fail("%s", f.what()); }
     int dev = 0, cus = 0;
     MFX_HIP(hipGetDevice(&dev));
     MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -552,6 +591,11 @@ static int qnet_run(QNetHandle* q, const float* view, size_t view_ld, const floa
                                            : (const void*)(static_cast<const float*>(prob) + (size_t)off * prob_ld);
         float* qo = q_out ? q_out + (size_t)off * q->dev.A : nullptr;
         int32_t* ao = act ? (r.rows ? act : act + off) : nullptr;
+        if (b16) {
+            MFX_HIP(qb16_forward(q->b16, v, view_ld, f, feat_ld, pb, prob_f64, prob_ld, r, m,
+                                 reinterpret_cast<uint16_t*>(q->conv.p), qo, ao, d_n, off, st));
+            continue;
+        }
         const int cgrid = std::min((m + kQConv2Agents - 1) / kQConv2Agents, cus);
         k_qnet_conv2<<<cgrid, 512, kQConvSmem, st>>>(q->dev, v, view_ld, r.rows, m, q->conv.p, d_n, off);
         MFX_HIP(hipGetLastError());

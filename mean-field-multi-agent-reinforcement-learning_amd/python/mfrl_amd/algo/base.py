@@ -28,6 +28,7 @@ def weights_key(net, gen=0):
 
 class ValueNet:
     graph_train = True          # train() replays the minibatch step as a HIP graph (train_batches)
+    act_precision = "f32"       # act_dev's HIP forward: "f32", or "bf16" operands (mfrl_amd.policy); training stays f32
 
     def __init__(self, sess, env, handle, name, update_every=5, use_mf=False, learning_rate=1e-4, tau=0.005,
                  gamma=0.95):
@@ -171,8 +172,8 @@ class ValueNet:
     @torch.no_grad()
     def act_dev(self, **kwargs):
         """Device in, device out: int32 greedy actions (algo/base.py:228-254).  The Battle view runs the
-        hand-written HIP forward (mfrl_amd.policy.QNetHIP, csrc/policy_kernels.hip) with the eval net's
-        current weights: argmax of e_q, the reference's argmax softmax(e_q / temperature) up to float ties.
+        hand-written HIP forward (mfrl_amd.policy.QNetHIP, csrc/policy_kernels.hip; act_precision = "bf16":
+        csrc/qnet_bf16_kernels.hip) with the eval net's current weights: argmax of e_q, the reference's argmax softmax(e_q / temperature) up to float ties.
         Other view shapes (not in the shipped configs) run the torch module."""
         view, feat = as_dev(kwargs["state"][0]), as_dev(kwargs["state"][1])
         self.temperature = kwargs["eps"]
@@ -180,9 +181,11 @@ class ValueNet:
         if self.use_mf:
             assert len(prob) == len(view)
         if self.view_space == (13, 13, 7) and self.num_actions <= 32:
-            if getattr(self, "_hip", None) is None:
+            if getattr(self, "_hip", None) is None or self._hip.precision != self.act_precision:
                 from ..policy import QNetHIP
-                self._hip = QNetHIP(self.view_space, self.feature_space, self.num_actions, self.use_mf)
+                self._hip = QNetHIP(self.view_space, self.feature_space, self.num_actions, self.use_mf,
+                                    precision=self.act_precision)
+                self._hip_key = None
             key = weights_key(self.eval_net, self._wgen)
             if key != self._hip_key:                     # the weights train() last left, packed once
                 self._hip.load(self.eval_net)

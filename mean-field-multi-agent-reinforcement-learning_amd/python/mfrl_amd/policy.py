@@ -1,4 +1,5 @@
-"""QNetHIP: the hand-written HIP forward (csrc/policy_kernels.hip) of the reference's Q network.
+"""QNetHIP: the hand-written HIP forward (csrc/policy_kernels.hip, csrc/qnet_bf16_kernels.hip) of the reference's
+Q network.
 
     ValueNet._construct_net  examples/battle_model/algo/base.py:123-183   -> QNetHIP.forward (q values)
     ValueNet.act             examples/battle_model/algo/base.py:228-254   -> QNetHIP.act (argmax q)
@@ -9,8 +10,16 @@ the im2col / NHWC-flatten orders of TF (conv kernels [ky][kx][ci][co], Dense-Obs
 K padded to a multiple of 4 with zero rows -- and uploads them in one copy.  Forward only: training keeps
 the torch module (autograd); after an optimiser step call ``load`` again.
 
-Numerics: f32 inputs and weights, f32 MFMA accumulation (one rounding per product); the result differs
-from the torch module's by summation order only (|dq| ~1e-6 at these sizes, tests/test_policy_gpu.py).
+Numerics, precision="f32" (the default): f32 inputs and weights, f32 MFMA accumulation (one rounding per
+product); the result differs from the torch module's by summation order only (|dq| ~1e-6 at these sizes,
+tests/test_policy_gpu.py).
+
+precision="bf16" (opt-in, acting only): the operands of every matrix product -- the weights, the inputs and
+each layer's activation after bias and ReLU -- are rounded to bf16 (nearest even); products accumulate in f32,
+biases and ReLU stay f32, the Q values are written unrounded.  The Q values then differ from the f32 ones by
+the quantisation error (a few 1e-3 of the Q scale, tests/test_policy_bf16_cpu.py), so the greedy action can
+differ where the top two Q values are that close.  The contract is stated in csrc/qnet_bf16_kernels.hip and
+restated in numpy in tests/qnet_bf16_ref.py.
 """
 import ctypes
 
@@ -36,6 +45,8 @@ def rows_scratch(E, rowcap):
 def _stream():
     return _P(torch.cuda.current_stream().cuda_stream)
 
+
+PRECISIONS = {"f32": 0, "bf16": 1}      # mfx_qnet_set_precision
 
 N_BLOCKS = 18      # w1 b1 w2 b2 wd bd we be wp1 bp1 wp2 bp2 w2d b2d wo bo wq bq (policy_kernels.hip)
 
@@ -93,12 +104,15 @@ def pack_qnet(net, feature, n_action, use_mf, layout=None):
 
 
 class QNetHIP:
-    def __init__(self, view_space, feature_space, num_actions, use_mf=False):
+    def __init__(self, view_space, feature_space, num_actions, use_mf=False, precision="f32"):
+        if precision not in PRECISIONS:
+            raise ValueError("QNetHIP: precision %r (one of %s)" % (precision, ", ".join(PRECISIONS)))
+        self.precision = precision
         h, w, c = view_space
         self.F, self.A, self.use_mf = int(feature_space[0]), int(num_actions), bool(use_mf)
         L = lib()
         for fn in ("mfx_qnet_create", "mfx_qnet_destroy", "mfx_qnet_set_weights", "mfx_qnet_forward",
-                   "mfx_qnet_act_rollout"):
+                   "mfx_qnet_act_rollout", "mfx_qnet_set_precision", "mfx_qnet_precision"):
             getattr(L, fn).restype = ctypes.c_int
         self._L = L
         self.blob_n, self.offsets = blob_layout(self.F, self.A, self.use_mf)
@@ -107,6 +121,8 @@ class QNetHIP:
               "mfx_qnet_create")
         self.handle = hdl
         self._rows = None
+        if precision != "f32":
+            check(L.mfx_qnet_set_precision(hdl, PRECISIONS[precision], _P()), "mfx_qnet_set_precision")
 
     def __del__(self):
         if getattr(self, "handle", None) is not None and self.handle.value:

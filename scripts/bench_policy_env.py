@@ -8,7 +8,8 @@ plans runs k_rollout_big<ext> + k_observe_items), timed with device events on th
 --agents N: two blocks of N / 2 (tests/battle_driver.block_positions, bench.py's placement); 0 (default): the
 reference's generate_map placement (4 % of the cells).  Prints one JSON line: agent-steps/s over the timed window
 (host clock around the window, ending in a synchronise), the forward's and the env step's (step + observation)
-device-event time per loop step, and check.ok: after the clock, sampled envs are replayed on the C oracle from
+device-event time per loop step, the network's precision (--precision f32 | bf16: QNetHIP's acting mode; with bf16 also
+f32_action_agreement, the share of live agents whose action on the final observation is the f32 network's), and check.ok: after the clock, sampled envs are replayed on the C oracle from
 rollout_init with the actions the device recorded at every step (warm-up included), and the final views, features,
 rewards, mean actions and group sizes must agree bit for bit.
 
@@ -36,6 +37,7 @@ ap.add_argument("--max-steps", type=int, default=400)
 ap.add_argument("--check-envs", type=int, default=4)
 ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--rush-step", action="store_true")
+ap.add_argument("--precision", choices=["f32", "bf16"], default="f32")
 a = ap.parse_args()
 
 import numpy as np  # noqa: E402
@@ -98,11 +100,13 @@ from mfrl_amd.algo.nets import QNet  # noqa: E402
 from mfrl_amd.policy import QNetHIP  # noqa: E402
 
 F, NA = 34, 21
-pols = []
+pols, nets = [], []
 for g in range(2):
     torch.manual_seed(a.seed + g)
-    pols.append(QNetHIP((13, 13, 7), (F,), NA, True).load(QNet((13, 13, 7), (F,), NA, True).cuda()))
+    nets.append(QNet((13, 13, 7), (F,), NA, True).cuda())
+    pols.append(QNetHIP((13, 13, 7), (F,), NA, True, precision=a.precision).load(nets[g]))
 res["policy_path"] = eng.rollout_policy_path()
+res["precision"] = a.precision
 picks = rck.sample_envs(E, a.check_envs)
 # the sampled envs' actions of every step since rollout_init, copied on the engine's stream after each forward
 log = torch.empty((T, len(picks), 2, rc), dtype=torch.int32, device="cuda")
@@ -145,6 +149,19 @@ res.update({"mode": "policy", "agent_steps_per_s": (n1 - n0) / wall, "loop_ms": 
 eng.rollout_check()
 dev = rck.device_records(eng, picks)
 acts = log.cpu().numpy()
+if a.precision != "f32":
+    # one more act on the final observation in both precisions: the share of live agents whose action is the f32 one
+    num = torch.empty((E, 2), dtype=torch.int32, device="cuda")
+    eng.rollout_copy("group_num", num)
+    both = []
+    for ps in (pols, [QNetHIP((13, 13, 7), (F,), NA, True).load(n) for n in nets]):
+        for g in range(2):
+            ps[g].act_rollout(eng, g)
+        both.append(torch.empty((E, 2, rc), dtype=torch.int32, device="cuda"))
+        eng.rollout_copy("actions", both[-1])
+    eng.sync()
+    live = torch.arange(rc, device="cuda")[None, None, :] < num[:, :, None]
+    res["f32_action_agreement"] = {"agents": int(live.sum()), "share": float((both[0] == both[1])[live].float().mean())}
 bad = []
 for j, e in enumerate(picks):
     o, h = common.battle_env(common.ORACLE_LIB, a.map)
