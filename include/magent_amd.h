@@ -122,7 +122,11 @@ int mfx_battle_rollout_step(void *game, int n_steps);
  * steps in one launch.  rollout_step(n) gives identical results for every value.  get: the value in force. */
 int mfx_battle_rollout_set_substeps(void *game, int n_sub);
 int mfx_battle_rollout_get_substeps(void *game, int *n_sub);
-/* names: view, feature, actions, rewards, mean_action, episode_return, stats, agent_steps, group_num */
+/* names: view, feature, actions, rewards, mean_action, episode_return, stats, agent_steps, group_num, ids, alive.
+ * ids (int32 [E][G][rowcap]) and alive (uint8 [E][G][rowcap]) are written by mfx_battle_rollout_policy_step only
+ * (mfx_battle_rollout_step leaves them alone): row i of group g of env e holds what mfx_battle_get's id / alive
+ * getters would report for that member after the step and before clear_dead -- the row order of actions and
+ * rewards.  Copyable (rollout_copy / rollout_copy_at), not writable. */
 int mfx_battle_rollout_buffer(void *game, const char *name, int group, void **d_ptr, size_t *bytes);
 int mfx_battle_rollout_copy(void *game, const char *name, int group, void *dst, size_t bytes);
 /* bytes [offset, offset + bytes) of a rollout buffer (e.g. one env's rows), async on the engine stream */
@@ -272,6 +276,48 @@ int mfx_rows_copy_shift(int n_cols, void *const *dst, const void *const *src, co
                         const int64_t *d_idx, int64_t src_mod, int64_t src_rows, int64_t dst_start, int64_t dst_cap,
                         int64_t n, uint32_t shift_mask, int64_t shift, void *stream);
 int mfx_rows_copy_error(int64_t *bad_index, void *stream);
+
+/* Replay rows straight from the device rollout loop (csrc/collect_kernels.hip): one row of the step-row columns per
+ * live agent of one group for every mfx_battle_rollout_policy_step, with no host work per step.
+ *   mfx_collect_begin  after the policy's actions are in the action buffer, before the policy step: builds the
+ *                      compact live-row list of the group (mfx_rollout_rows, into d_rows / d_total: E * rowcap ints
+ *                      and 1 + ceil(E / 64) ints of the caller's own) and writes, for list entry k = row j of env e,
+ *                      row n + k of obs / feat / act, prob = (float) of the env's n_action doubles of mean (when
+ *                      dst->prob is not null), and the env's episode number stats[e][0] parked in key;
+ *   mfx_collect_end    after the policy step, same list: rew from rewards, term = !alive, key = mfx_collect_key(e,
+ *                      parked episode number, ids[row], n_envs, id_stride); then advances n by the list length behind
+ *                      the row writes on the same stream.
+ * d_state: two int64 on the device -- [0] the row counter n, [1] the sticky error word (bit 0: a step did not fit in
+ * dst->capacity rows: none of its rows was written and n did not move; bit 1: an id outside [0, id_stride)).  The
+ * bound is checked before any store.  mfx_collect_reset sets n and clears the error word.  Everything is launched
+ * on `stream` (the engine's); nothing is read back. */
+typedef struct mfx_collect_src {          /* the rollout buffers (mfx_battle_rollout_buffer) and their shape */
+    const float *view, *feat;             /* [E][rowcap][view_floats], [E][rowcap][feat_floats] of the group */
+    const int32_t *actions;               /* [E][G][rowcap] */
+    const float *rewards;                 /* [E][G][rowcap] */
+    const double *mean;                   /* [E][G][mean_stride] (may be null without prob) */
+    const double *stats;                  /* [E][4] */
+    const int32_t *counts;                /* [E][G] group_num */
+    const int32_t *ids;                   /* [E][G][rowcap] */
+    const uint8_t *alive;                 /* [E][G][rowcap] */
+    int32_t n_envs, n_groups, group, rowcap, view_floats, feat_floats, n_action, mean_stride;
+} mfx_collect_src;
+typedef struct mfx_collect_dst {          /* the step-row columns, `capacity` rows each */
+    float *obs, *feat;
+    int32_t *act;
+    float *rew;
+    uint8_t *term;                        /* 0 / 1 */
+    float *prob;                          /* [capacity][n_action], or null */
+    int64_t *key;
+    int64_t capacity;
+} mfx_collect_dst;
+int mfx_collect_reset(int64_t *d_state, int64_t n, void *stream);
+int mfx_collect_begin(const mfx_collect_src *src, const mfx_collect_dst *dst, int32_t *d_rows, int32_t *d_total,
+                      int64_t *d_state, void *stream);
+int mfx_collect_end(const mfx_collect_src *src, const mfx_collect_dst *dst, const int32_t *d_rows,
+                    const int32_t *d_total, int64_t *d_state, int64_t id_stride, void *stream);
+/* (episode * n_envs + env) * id_stride + id: injective over env < n_envs, episode >= 0, id < id_stride (host) */
+int64_t mfx_collect_key(int64_t env, int64_t episode, int64_t id, int64_t n_envs, int64_t id_stride);
 
 /* ---------------------------------------------------------------- measurement */
 /* The HBM write ceiling on this device, measured in-process beside the bench (csrc/diag_kernels.hip): total_bytes

@@ -511,6 +511,13 @@ __device__ __forceinline__ void agent_phase(const GameParams& gp, const State& s
         for (int i = TID; i < n; i += team_lanes<kW>()) {
             const float r = v.next_r[v.grp_ids[g * cap + i]] + v.grp_reward[g];
             if (i < ra.rowcap) ra.rewards[((size_t)e * G + g) * ra.rowcap + i] = r;
+            if constexpr (kExt) {              // get_agent_id / get_alive before clear_dead (the replay collector)
+                if (i < ra.rowcap) {
+                    const int id = v.grp_ids[g * cap + i];
+                    ra.ids[((size_t)e * G + g) * ra.rowcap + i] = ref_id(v, id);
+                    ra.alive[((size_t)e * G + g) * ra.rowcap + i] = (uint8_t)!meta_dead(v.meta[id]);
+                }
+            }
             part += r;
         }
         const float tot = kW ? wave_sum(part) : block_sum_waves(part, red);

@@ -446,6 +446,13 @@ __device__ __forceinline__ void big_env_step(const GameParams& gp, const State& 
         for (int i = TID; i < n; i += blockDim.x) {
             const float r = v.next_r[v.grp_ids[g * cap + i]] + v.grp_reward[g];
             ra.rewards[((size_t)e * G + g) * ra.rowcap + i] = r;
+            if constexpr (kExt) {              // get_agent_id / get_alive before clear_dead (the replay collector)
+                if (i < ra.rowcap) {
+                    const int id = v.grp_ids[g * cap + i];
+                    ra.ids[((size_t)e * G + g) * ra.rowcap + i] = (int32_t)v.rid[id];
+                    ra.alive[((size_t)e * G + g) * ra.rowcap + i] = (uint8_t)!meta_dead(v.meta[id]);
+                }
+            }
             part += r;
         }
         ret[g] = block_sum_waves(part, red);

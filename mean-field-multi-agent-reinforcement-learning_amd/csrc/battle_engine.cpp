@@ -285,6 +285,8 @@ public:
     // The other form re-seeds on its next call, as after per-call calls (ro_prep_stale).
     int ro_prep_form = 0;
     DevBuf<int32_t> ro_actions, ro_eplen, ro_tx, ro_ty;
+    DevBuf<int32_t> ro_ids;                  // [E][G][rowcap] ids / alive flags of the last policy step (RolloutArgs::ids)
+    DevBuf<uint8_t> ro_alive;
     DevBuf<double> ro_mean, ro_stats;
     DevBuf<unsigned long long> ro_steps;
     DevBuf<int32_t> ro_work;                 // k_rollout work-queue counters (2)
@@ -380,6 +382,7 @@ public:
             q.feat[g] += e0 * rc * gp.feat_size[g];
         }
         q.actions += e0 * G * rc; q.rewards += e0 * G * rc; q.mean_act += (size_t)e0 * G * ra.mean_stride;
+        q.ids += e0 * G * rc; q.alive += e0 * G * rc;
         q.ep_return += (size_t)e0 * G; q.ep_len += e0; q.stats += (size_t)e0 * 4; q.agent_steps += e0;
         if (q.obs_mm) { q.obs_mm += (size_t)e0 * G * 169; q.obs_info += (size_t)e0 * s.cap; }
         q.env_base = e0;
@@ -405,6 +408,7 @@ public:
             q.feat[g] += e0 * rc * gp.feat_size[g];
         }
         q.actions += e0 * G * rc; q.rewards += e0 * G * rc; q.mean_act += (size_t)e0 * G * ra.mean_stride;
+        q.ids += e0 * G * rc; q.alive += e0 * G * rc;
         q.ep_return += (size_t)e0 * G; q.ep_len += e0; q.stats += (size_t)e0 * 4; q.agent_steps += e0;
         if (q.obs_mm) { q.obs_mm += (size_t)e0 * G * 169; q.obs_info += (size_t)e0 * s.cap; }
         q.env_base = e0;
@@ -1223,6 +1227,9 @@ public:
             for (int g = 0; g < G; g++) na = std::max(na, gtype(g).n_action);
             ro_actions.ensure((size_t)E * G * rowcap); ro_rewards.ensure((size_t)E * G * rowcap);
             ro_mean.ensure((size_t)E * G * na); ro_return.ensure((size_t)E * G); ro_eplen.ensure(E);
+            ro_ids.ensure((size_t)E * G * rowcap); ro_alive.ensure((size_t)E * G * rowcap);
+            MFX_HIP_THROW(hipMemset(ro_ids.p, 0, sizeof(int32_t) * E * G * rowcap));
+            MFX_HIP_THROW(hipMemset(ro_alive.p, 0, (size_t)E * G * rowcap));
             ro_stats.ensure((size_t)E * 4); ro_steps.ensure(E);
             MFX_HIP_THROW(hipMemset(ro_return.p, 0, sizeof(float) * E * G));
             MFX_HIP_THROW(hipMemset(ro_mean.p, 0, sizeof(double) * ro_mean.n));   // former_act_prob = 0 at step 0
@@ -1235,6 +1242,7 @@ public:
             MFX_HIP_THROW(hipMemset(ro_steps.p, 0, sizeof(unsigned long long) * E));
             a.rowcap = rowcap; a.actions = ro_actions.p; a.rewards = ro_rewards.p; a.mean_act = ro_mean.p;
             a.mean_stride = na;
+            a.ids = ro_ids.p; a.alive = ro_alive.p;
             a.ep_return = ro_return.p; a.ep_len = ro_eplen.p; a.stats = ro_stats.p; a.agent_steps = ro_steps.p;
             a.tmpl_x = ro_tx.p; a.tmpl_y = ro_ty.p; a.tmpl_cap = tcap;
             a.max_steps = max_steps; a.policy_seed = seed; a.step_index = 0; a.eps = eps;
@@ -1769,6 +1777,8 @@ public:
         else if (!strcmp(name, "feature")) { *ptr = ra.feat[group]; *bytes = E * rc * gp.feat_size[group] * 4; }
         else if (!strcmp(name, "actions")) { *ptr = ra.actions; *bytes = (size_t)E * G * rc * 4; }
         else if (!strcmp(name, "rewards")) { *ptr = ra.rewards; *bytes = (size_t)E * G * rc * 4; }
+        else if (!strcmp(name, "ids")) { *ptr = ra.ids; *bytes = (size_t)E * G * rc * 4; }
+        else if (!strcmp(name, "alive")) { *ptr = ra.alive; *bytes = (size_t)E * G * rc; }
         else if (!strcmp(name, "mean_action")) { *ptr = ra.mean_act; *bytes = ro_mean.n * 8; }
         else if (!strcmp(name, "episode_return")) { *ptr = ra.ep_return; *bytes = (size_t)E * G * 4; }
         else if (!strcmp(name, "stats")) { *ptr = ra.stats; *bytes = (size_t)E * 4 * 8; }

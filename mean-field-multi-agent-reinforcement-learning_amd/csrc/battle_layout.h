@@ -263,6 +263,11 @@ struct RolloutArgs {
                                     // install rebuilds the cells from it plus the agents' positions, so
                                     // per-env cells are neither read nor written back (State::cells is
                                     // rebuilt on demand, BattleEngine::sync_cells)
+    // A learned policy's steps only (k_rollout kMode 1, k_rollout_big<true>): what get_agent_id / get_alive report
+    // for each member after the step and before clear_dead, in the row order of actions / rewards (the replay
+    // collector's agent keys and terminal flags, csrc/collect_kernels.hip).  The rush forms never touch them.
+    int32_t* ids;                   // [E][G][rowcap]
+    uint8_t* alive;                 // [E][G][rowcap]
 };
 
 // XCDs of the MI355X (workgroup i of a launch runs on XCD i % kXcds) and the int32 pad of one

@@ -181,18 +181,37 @@ class ValueNet:
         if self.use_mf:
             assert len(prob) == len(view)
         if self.view_space == (13, 13, 7) and self.num_actions <= 32:
-            if getattr(self, "_hip", None) is None or self._hip.precision != self.act_precision:
-                from ..policy import QNetHIP
-                self._hip = QNetHIP(self.view_space, self.feature_space, self.num_actions, self.use_mf,
-                                    precision=self.act_precision)
-                self._hip_key = None
-            key = weights_key(self.eval_net, self._wgen)
-            if key != self._hip_key:                     # the weights train() last left, packed once
-                self._hip.load(self.eval_net)
-                self._hip_key = key
-            return self._hip.act(view, feat, prob)
+            return self._hip_current().act(view, feat, prob)
         e_q = self.eval_net(view, feat, prob)
         return torch.argmax(torch.softmax(e_q / self.temperature, dim=1), dim=1).to(torch.int32)
+
+    def _hip_current(self):
+        """The HIP forward (act_precision) holding the eval net's current weights: re-packed only when
+        weights_key moved."""
+        if getattr(self, "_hip", None) is None or self._hip.precision != self.act_precision:
+            from ..policy import QNetHIP
+            self._hip = QNetHIP(self.view_space, self.feature_space, self.num_actions, self.use_mf,
+                                precision=self.act_precision)
+            self._hip_key = None
+        key = weights_key(self.eval_net, self._wgen)
+        if key != self._hip_key:                     # the weights train() last left, packed once
+            self._hip.load(self.eval_net)
+            self._hip_key = key
+        return self._hip
+
+    @torch.no_grad()
+    def act_rollout(self, eng, group):
+        """Greedy actions of group `group` of a BattleBatch's rollout from its observation buffers into its action
+        buffer (mfrl_amd.policy.QNetHIP.act_rollout), with the eval net's current weights; nothing is read back.
+        The weights are uploaded on the caller's current stream: when they moved and the engine sits on another
+        stream, the engine's stream waits for the upload."""
+        if not (self.view_space == (13, 13, 7) and self.num_actions <= 32):
+            raise ValueError("act_rollout: the HIP forward takes the Battle view (13, 13, 7) and at most 32 actions")
+        before = self._hip_key
+        hip = self._hip_current()
+        if self._hip_key != before and eng.stream_handle() != torch.cuda.current_stream().cuda_stream:
+            eng.torch_stream().wait_stream(torch.cuda.current_stream())
+        hip.act_rollout(eng, group)
 
     def act(self, **kwargs):
         return self.act_dev(**kwargs).cpu().numpy().astype(np.int32)

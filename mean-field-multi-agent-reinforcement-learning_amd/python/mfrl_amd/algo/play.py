@@ -6,6 +6,8 @@
   from the engine's buffers straight into the policy forward, actions straight back into
   set_action, and the replay rows into the device MemoryGroup / EpisodesBuffer (SURVEY.md 8(f)
   rows 1-2).  Agent keys in the buffers are env * cap + id.
+* play_rollout: a round on the device rollout loop (act_rollout + rollout_policy_step, no host round trip
+  per step), the replay rows collected by mfrl_amd.replay.RolloutCollector (DQN / MFQ).
 """
 import math
 import random
@@ -191,4 +193,77 @@ def play_batched(eng, n_round, map_size, max_steps, models, print_every=50, eps=
     for g in range(G):
         mean_rewards[g] = sum(mean_rewards[g]) / max(len(mean_rewards[g]), 1)
         total_rewards[g] = sum(total_rewards[g])
+    return max_nums, nums, mean_rewards, total_rewards
+
+
+def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, train=False, left_id=None):
+    """One round of max_steps steps on all E envs of `eng` on the device rollout loop: ValueNet.act_rollout for both
+    groups, BattleBatch.rollout_policy_step, and -- with train -- group 0's replay rows collected by a
+    mfrl_amd.replay.RolloutCollector around every step, then models[0].train().  No host synchronisation inside
+    the loop.  Q-learning models only (DQN, MFQ: a MemoryGroup replay buffer); others are refused.
+
+    Unlike play_batched, which idles an env once it is done, an env that ends early (done, or max_steps steps into
+    its episode) restarts inside the loop from the same placement and keeps producing rows: every round is exactly
+    max_steps steps of every env.  The greedy policy does not use eps (as in play_batched).
+
+    Returns (max_nums, nums, mean_rewards, total_rewards) summed over envs like play_batched, computed once at the
+    end from the rollout's stats, episode_return and group_num buffers: total_rewards[g] is the return of every
+    episode of the round (finished or running); mean_rewards[g] is that per agent-step, both groups' agent-steps
+    counted evenly (the engine counts agent-steps per env, not per group)."""
+    from ..replay import RolloutCollector
+    from .tools import MemoryGroup
+    E, G = eng.n_envs, 2
+    for m in models[:G]:
+        if not hasattr(m, "act_rollout"):
+            raise TypeError("play_rollout: %s has no device rollout forward (DQN / MFQ only)" % type(m).__name__)
+    if train and not isinstance(getattr(models[0], "replay_buffer", None), MemoryGroup):
+        raise TypeError("play_rollout: %s does not train from a MemoryGroup (DQN / MFQ only; EpisodesBuffer "
+                        "consumes host randomness per push)" % type(models[0]).__name__)
+    left, right = block_positions(map_size)
+    left_id = random.randint(0, 1) if left_id is None else left_id
+    placement = [None, None]
+    placement[left_id], placement[1 - left_id] = left, right
+    eng.reset()
+    eng.rollout_init(placement, max_steps=max_steps, eps=0.0, seed=n_round, stagger=False)
+    if eng.rollout_policy_path() is None:
+        raise RuntimeError("play_rollout: this rollout plan takes no learned policy (MFX_ROLLOUT_PIPE=1)")
+    eng.rollout_policy_observe()
+    col = None
+    if train:
+        col = getattr(models[0], "_rollout_collector", None)
+        if col is None or col.eng is not eng or col.mg is not models[0].replay_buffer:
+            col = models[0]._rollout_collector = RolloutCollector(eng, models[0].replay_buffer, 0)
+    max_nums = [len(placement[g]) * E for g in range(G)]
+    print("\n\n[*] ROUND #{0}, EPS: {1:.2f} NUMBER: {2} ({3} envs, device rollout)".format(n_round, eps, max_nums, E))
+    t_play = time.time()
+    for step_ct in range(max_steps):
+        for g in range(G):
+            models[g].act_rollout(eng, g)
+        if col is not None:
+            col.begin()
+        eng.rollout_policy_step()
+        if col is not None:
+            col.end()
+    rows = col.finish() if col is not None else 0
+    eng.rollout_check()
+    t_play = time.time() - t_play
+    stats = torch.empty((E, 4), dtype=torch.float64, device="cuda")
+    ret = torch.empty((E, G), dtype=torch.float32, device="cuda")
+    num = torch.empty((E, G), dtype=torch.int32, device="cuda")
+    steps = torch.empty(E, dtype=torch.int64, device="cuda")
+    for name, buf in (("stats", stats), ("episode_return", ret), ("group_num", num), ("agent_steps", steps)):
+        eng.rollout_copy(name, buf)
+    eng.sync()
+    agent_steps = int(steps.sum().item())
+    nums = [int(x) for x in num.sum(0).tolist()]
+    total_rewards = [float(stats[:, 1 + g].sum().item()) + float(ret[:, g].double().sum().item()) for g in range(G)]
+    mean_rewards = [total_rewards[g] / max(agent_steps / G, 1.0) for g in range(G)]
+    t_train = time.time()
+    if train:
+        models[0].train()
+        torch.cuda.synchronize()
+    print("[TIME] play {} steps x {} envs: {:.2f} s ({:.3g} agent-steps/s incl. policy forward); train {:.2f} s"
+          .format(max_steps, E, t_play, agent_steps / max(t_play, 1e-9), time.time() - t_train))
+    if train:
+        print("[INFO] device rollout: {} replay rows, {} episodes finished".format(rows, int(stats[:, 0].sum().item())))
     return max_nums, nums, mean_rewards, total_rewards

@@ -115,18 +115,21 @@ class _StepRows:
         self.cap = 0
         self.cols = {}
 
-    def _ensure(self, need):
+    def _ensure(self, need, live=None):
+        """Storage for `need` rows; a grow carries the first `live` rows over (default: the n rows pushed -- the
+        rollout collector passes its upper bound, its exact count being on the device)."""
         if need <= self.cap:
             return
+        live = self.n if live is None else min(int(live), self.cap)
         cap = max(need, 2 * self.cap, 1024)
         spec = {"ids": ((), torch.int64), "obs": (self.obs_shape, torch.float32), "feat": (self.feat_shape, torch.float32),
                 "act": ((), torch.int32), "rew": ((), torch.float32), "term": ((), torch.bool)}
         if self.use_mean:
             spec["prob"] = ((self.act_n,), torch.float32)
         new = {k: torch.empty((cap,) + s, dtype=d, device=self.device) for k, (s, d) in spec.items()}
-        if self.n:
+        if live:
             keys = list(self.cols)
-            _move([new[k] for k in keys], [self.cols[k] for k in keys], n=self.n)
+            _move([new[k] for k in keys], [self.cols[k] for k in keys], n=live)
         self.cols, self.cap = new, cap
 
     def push(self, ids, obs, feat, act, rew, alive, prob=None, order=None):

@@ -61,6 +61,14 @@ class BattleBatch:
         """The hipStream_t the engine launches on (0: the null stream)."""
         return getattr(self, "_stream_raw", 0) or 0
 
+    def torch_stream(self):
+        """The same stream as a torch stream (for torch work that must be ordered with the engine's launches)."""
+        import torch
+        raw = self.stream_handle()
+        if getattr(self, "_torch_stream", (None, None))[0] != raw:
+            self._torch_stream = (raw, torch.cuda.ExternalStream(raw) if raw else torch.cuda.default_stream())
+        return self._torch_stream[1]
+
     # ------------------------------------------------------------------ reference call sequence
     def reset(self):
         self.env.reset()

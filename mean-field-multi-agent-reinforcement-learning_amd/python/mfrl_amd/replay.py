@@ -47,6 +47,154 @@ def rows_copy(dst, src, idx=None, src_mod=0, dst_start=0, dst_cap=0, n=None, shi
           "mfx_rows_copy_shift")
 
 
+def rollout_key(env, episode, agent_id, n_envs, id_stride):
+    """The agent key of a collected row (csrc/collect_kernels.hip collect_key): injective over env < n_envs,
+    episode >= 0 and agent_id < id_stride.  Ids restart at 0 in every episode, so the episode number is part of it."""
+    return (episode * n_envs + env) * id_stride + agent_id
+
+
+class _CollectSrc(ctypes.Structure):      # mfx_collect_src (include/magent_amd.h)
+    _fields_ = ([(k, ctypes.c_void_p) for k in ("view", "feat", "actions", "rewards", "mean", "stats", "counts", "ids",
+                                                  "alive")] +
+                [(k, ctypes.c_int32) for k in ("n_envs", "n_groups", "group", "rowcap", "view_floats", "feat_floats",
+                                               "n_action", "mean_stride")])
+
+
+class _CollectDst(ctypes.Structure):      # mfx_collect_dst
+    _fields_ = ([(k, ctypes.c_void_p) for k in ("obs", "feat", "act", "rew", "term", "prob", "key")] +
+                [("capacity", ctypes.c_int64)])
+
+
+class CollectOverflow(RuntimeError):
+    pass
+
+
+class RolloutCollector:
+    """Replay rows of group `group` straight from a BattleBatch's device rollout loop into a MemoryGroup's step rows
+    (algo/tools.py _StepRows), one row per live agent per rollout_policy_step, on the HIP kernels of
+    csrc/collect_kernels.hip:
+
+        policy.act_rollout(eng, g) ...      # the actions are in the rollout's action buffer
+        col.begin()                         # view, feature, action, former mean action, episode number
+        eng.rollout_policy_step()
+        col.end()                           # reward, terminal = !alive, key; the device row counter advances
+        ...
+        col.finish()                        # one synchronise: _StepRows.n = the counter; raises on overflow
+
+    after which MemoryGroup.tight() / get_batch_num() / sample() and ValueNet.train_batches run unchanged.  Nothing is
+    read back between the first begin() and finish(): the row count is on the device, so begin() reserves storage for
+    the worst case of one more step (E * rowcap rows past a running upper bound of the count; geometric growth, the
+    grow copy moves the rows up to the bound).  Every launch, allocation and copy is ordered on the engine's stream
+    (eng.stream_handle()), whatever stream the caller is on.  capacity: never write a row at or past this index (a
+    step that would is dropped whole and finish() raises CollectOverflow); None: grow as needed."""
+
+    def __init__(self, eng, memory_group, group=0, capacity=None):
+        self.eng, self.mg, self.group, self.capacity = eng, memory_group, int(group), capacity
+        self._bound = None                  # upper bound of the device row counter; None: no step since finish()
+        self._state = self._scratch = None
+        self._src = self._dst = None
+        if memory_group._rows.device != "cpu":
+            L = lib()
+            for fn in ("mfx_collect_reset", "mfx_collect_begin", "mfx_collect_end"):
+                getattr(L, fn).restype = ctypes.c_int
+            self._L = L
+
+    # ---- host bookkeeping (runs without a GPU)
+    def step_rows(self):
+        """Worst-case rows of one step: every row slot of the group in every env."""
+        return self.eng.n_envs * self.eng.rowcap
+
+    def id_stride(self):
+        """Ids of an episode are below this: no more agents than row slots over all groups."""
+        return len(self.eng.handles) * self.eng.rowcap
+
+    def _reserve(self):
+        """Storage for one more step past the bound; returns the capacity in rows the kernels may write."""
+        rows = self.mg._rows
+        if self._bound is None:
+            self._bound = rows.n
+        need = self._bound + self.step_rows()
+        if self.capacity is not None:
+            need = min(need, int(self.capacity))
+        old = list(rows.cols.values()) if need > rows.cap else []
+        rows._ensure(need, live=self._bound)
+        for t in old:                       # the old columns may still be read by the grow copy on this stream
+            if t.is_cuda:
+                t.record_stream(torch.cuda.current_stream())
+        self._bound = min(self._bound + self.step_rows(), rows.cap)
+        return rows.cap if self.capacity is None else min(rows.cap, int(self.capacity))
+
+    # ---- device
+    def _buffer(self, name, group=0):
+        p, nb = ctypes.c_void_p(), ctypes.c_size_t()
+        self.eng._check(self.eng._dll.mfx_battle_rollout_buffer(self.eng.game, name.encode(), group, ctypes.byref(p),
+                                                                ctypes.byref(nb)), "rollout_buffer")
+        return p.value
+
+    def begin(self):
+        eng, rows = self.eng, self.mg._rows
+        E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
+        st = ctypes.c_void_p(eng.stream_handle())
+        with torch.cuda.stream(self.eng.torch_stream()):
+            fresh = self._bound is None
+            if self._state is None:
+                self._state = torch.zeros(2, dtype=torch.int64, device="cuda")
+            if self._scratch is None or self._scratch.numel() < E * rc + 1 + (E + 63) // 64:
+                self._scratch = torch.empty(E * rc + 1 + (E + 63) // 64, dtype=torch.int32, device="cuda")
+            cap = self._reserve()
+            if fresh:
+                check(self._L.mfx_collect_reset(ctypes.c_void_p(self._state.data_ptr()), ctypes.c_int64(rows.n), st),
+                      "mfx_collect_reset")
+        V = 1
+        for x in rows.obs_shape:
+            V *= int(x)
+        F = 1
+        for x in rows.feat_shape:
+            F *= int(x)
+        g = self.group
+        self._src = _CollectSrc(self._buffer("view", g), self._buffer("feature", g), self._buffer("actions"),
+                                self._buffer("rewards"), self._buffer("mean_action"), self._buffer("stats"),
+                                self._buffer("group_num"), self._buffer("ids"), self._buffer("alive"),
+                                E, G, g, rc, V, F, int(rows.act_n), eng.mean_stride())
+        c = rows.cols
+        self._dst = _CollectDst(c["obs"].data_ptr(), c["feat"].data_ptr(), c["act"].data_ptr(), c["rew"].data_ptr(),
+                                c["term"].data_ptr(), c["prob"].data_ptr() if rows.use_mean else None,
+                                c["ids"].data_ptr(), cap)
+        self._ptrs = (ctypes.c_void_p(self._scratch.data_ptr()), ctypes.c_void_p(self._scratch.data_ptr() + 4 * E * rc),
+                      ctypes.c_void_p(self._state.data_ptr()))
+        check(self._L.mfx_collect_begin(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs, st),
+              "mfx_collect_begin")
+
+    def end(self):
+        assert self._src is not None, "RolloutCollector.end() without begin()"
+        check(self._L.mfx_collect_end(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs,
+                                      ctypes.c_int64(self.id_stride()), ctypes.c_void_p(self.eng.stream_handle())),
+              "mfx_collect_end")
+        self._src = None
+
+    def discard(self):
+        """Drop the rows collected since the last finish() without reading anything back: the next begin() restarts
+        the device counter at _StepRows.n (and clears the error word)."""
+        self._bound = None
+
+    def finish(self):
+        """Synchronise the engine's stream once; the step rows now hold the collected rows (returns their number).
+        Raises CollectOverflow when a step did not fit below `capacity` (its rows were dropped; _StepRows.n is left
+        as it was before the first begin())."""
+        if self._bound is None:
+            return self.mg._rows.n
+        with torch.cuda.stream(self.eng.torch_stream()):
+            n, err = self._state.cpu().tolist()
+        self._bound = None
+        if err:
+            raise CollectOverflow("RolloutCollector: %s" % ("a step's rows did not fit below the capacity of %s rows"
+                                                            % self.capacity if err & 1 else
+                                                            "an agent id outside [0, %d)" % self.id_stride()))
+        self.last_rows = int(n) - self.mg._rows.n      # rows of this session (begin() of its first step .. finish())
+        self.mg._rows.n = int(n)
+        return int(n)
+
+
 def check_errors():
     """Synchronise the current stream; raise IndexError if a rows_copy since the last check met a source
     index outside its source rows (that row was skipped)."""

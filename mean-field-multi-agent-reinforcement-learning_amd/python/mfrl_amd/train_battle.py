@@ -2,6 +2,7 @@
 
     python -m mfrl_amd.train_battle --algo mfq --n_round 2000 --map_size 40 --max_steps 400
     python -m mfrl_amd.train_battle --algo mfq --envs 256 ...     # batched engine, all in HBM
+    python -m mfrl_amd.train_battle --algo mfq --envs 256 --rollout ...   # the device rollout loop (mfq / il)
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -16,7 +17,7 @@ import torch
 import magent
 
 from .algo import spawn_ai, tools
-from .algo.play import play, play_batched
+from .algo.play import play, play_batched, play_rollout
 
 
 def linear_decay(epoch, x, y):
@@ -45,7 +46,13 @@ def main(argv=None):
     parser.add_argument("--max_steps", type=int, default=400)
     parser.add_argument("--envs", type=int, default=1, help="envs per round (>1: batched engine in HBM)")
     parser.add_argument("--base_dir", type=str, default=os.getcwd())
+    parser.add_argument("--rollout", action="store_true",
+                        help="with --envs > 1: act, step and collect replay rows on the device rollout loop (mfq / il)")
     args = parser.parse_args(argv)
+    if args.rollout and args.envs <= 1:
+        parser.error("--rollout needs the batched engine: --envs > 1")
+    if args.rollout and args.algo not in ("mfq", "il"):
+        parser.error("--rollout collects into a MemoryGroup: --algo mfq or il (ac / mfac train from an EpisodesBuffer)")
 
     env = magent.GridWorld("battle", map_size=args.map_size)
     env.set_render_dir(os.path.join(args.base_dir, "examples/battle_model", "build/render"))  # train_battle.py:87
@@ -64,7 +71,8 @@ def main(argv=None):
 
         def play_handle(env, n_round, map_size, max_steps, handles, models, print_every, eps=1.0, render=False,
                         train=False):
-            return play_batched(eng, n_round, map_size, max_steps, models, print_every, eps, train)
+            loop = play_rollout if args.rollout else play_batched
+            return loop(eng, n_round, map_size, max_steps, models, print_every, eps, train)
     runner = tools.Runner(None, env, handles, args.map_size, args.max_steps, models, play_handle,
                           render_every=args.save_every if args.render else 0, save_every=args.save_every, tau=0.01,
                           log_name=args.algo, log_dir=log_dir, model_dir=model_dir, train=True)

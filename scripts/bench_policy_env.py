@@ -13,6 +13,12 @@ f32_action_agreement, the share of live agents whose action on the final observa
 rollout_init with the actions the device recorded at every step (warm-up included), and the final views, features,
 rewards, mean actions and group sizes must agree bit for bit.
 
+--collect: run a mfrl_amd.replay.RolloutCollector for group 0 (into an MF-Q MemoryGroup's step rows) around every
+policy step of the loop, warm-up included: the record gains collect_ms (begin + end, device events), rows_per_step,
+row_bytes and the collector's achieved bytes per second (read + write of the row bytes), and is appended to
+profiles/policy_env_steps.jsonl.  When the rows of all steps would not fit in --collect-gb of HBM, every step's rows
+are dropped again before the next (RolloutCollector.discard: the device counter restarts, nothing is read back).
+
 --rush-step: time rollout_step(1) launches instead (the on-device rush policy; no network).  With MFX_BIG_FUSED=0 it
 runs the same two kernels as the policy form's env step, on two sub-batch streams: the yardstick that step is
 compared with.  Works with older builds of the library (MAGENT_LIB)."""
@@ -38,6 +44,8 @@ ap.add_argument("--check-envs", type=int, default=4)
 ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--rush-step", action="store_true")
 ap.add_argument("--precision", choices=["f32", "bf16"], default="f32")
+ap.add_argument("--collect", action="store_true")
+ap.add_argument("--collect-gb", type=float, default=48.0)
 a = ap.parse_args()
 
 import numpy as np  # noqa: E402
@@ -112,6 +120,14 @@ picks = rck.sample_envs(E, a.check_envs)
 log = torch.empty((T, len(picks), 2, rc), dtype=torch.int32, device="cuda")
 
 
+col, ROW_BYTES = None, 4 * (13 * 13 * 7 + F + 1 + 1 + NA) + 1 + 8      # view, feature, action, reward, prob; term; key
+if a.collect:
+    from mfrl_amd.algo.tools import MemoryGroup  # noqa: E402
+    from mfrl_amd.replay import RolloutCollector  # noqa: E402
+    col = RolloutCollector(eng, MemoryGroup((13, 13, 7), (F,), NA, 1024, 64, a.max_steps, use_mean=True), 0)
+    col_keep = T * E * rc * ROW_BYTES <= a.collect_gb * 1e9
+
+
 def loop_step(t, ev=None):
     if ev:
         ev[0].record()
@@ -121,18 +137,30 @@ def loop_step(t, ev=None):
         ev[1].record()
     for j, e in enumerate(picks):
         eng.rollout_copy_at("actions", log[t, j], e * 2 * rc * 4)
+    if col:
+        if not col_keep:
+            col.discard()
+        if ev:
+            ev[4].record()
+        col.begin()
+        if ev:
+            ev[5].record()
     if ev:
         ev[2].record()
     eng.rollout_policy_step()
     if ev:
         ev[3].record()
+    if col:
+        col.end()
+        if ev:
+            ev[6].record()
 
 
 eng.rollout_policy_observe()
 for t in range(a.warmup):
     loop_step(t)
 n0 = agent_steps()
-ev = [events(4) for _ in range(a.steps)]
+ev = [events(7) for _ in range(a.steps)]
 t0 = time.perf_counter()
 for k in range(a.steps):
     loop_step(a.warmup + k, ev[k])
@@ -144,6 +172,17 @@ env = [x[2].elapsed_time(x[3]) for x in ev]
 res.update({"mode": "policy", "agent_steps_per_s": (n1 - n0) / wall, "loop_ms": 1e3 * wall / a.steps,
             "forward_ms": {"mean": statistics.fmean(fwd), "median": statistics.median(fwd)},
             "env_step_ms": {"mean": statistics.fmean(env), "median": statistics.median(env), "max": max(env)}})
+
+if col:
+    n_rows = col.finish()
+    per_step = n_rows / (T if col_keep else 1)
+    cms = [x[4].elapsed_time(x[5]) + x[3].elapsed_time(x[6]) for x in ev]
+    med = statistics.median(cms)
+    res.update({"collect": True, "collect_kept_all_steps": col_keep, "rows_per_step": per_step, "row_bytes": ROW_BYTES,
+                "collect_ms": {"mean": statistics.fmean(cms), "median": med, "max": max(cms),
+                               "begin_median": statistics.median(x[4].elapsed_time(x[5]) for x in ev),
+                               "end_median": statistics.median(x[3].elapsed_time(x[6]) for x in ev)},
+                "collect_gb_per_s": 2 * per_step * ROW_BYTES / (med * 1e-3) / 1e9})
 
 # ---------------------------------------------------------------- after the clock: the oracle replay
 eng.rollout_check()
@@ -206,4 +245,8 @@ for j, e in enumerate(picks):
             bad.append("env %d group %d: mean action" % (e, g))
 res["check"] = {"ok": not bad, "envs": picks, "steps": T, "bad": bad[:8]}
 print(json.dumps(res))
+if col:
+    os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
+    with open(os.path.join(REPO, "profiles", "policy_env_steps.jsonl"), "a") as f:
+        f.write(json.dumps(res) + "\n")
 sys.exit(0 if not bad else 1)
