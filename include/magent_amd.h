@@ -319,6 +319,56 @@ int mfx_collect_end(const mfx_collect_src *src, const mfx_collect_dst *dst, cons
 /* (episode * n_envs + env) * id_stride + id: injective over env < n_envs, episode >= 0, id < id_stride (host) */
 int64_t mfx_collect_key(int64_t env, int64_t episode, int64_t id, int64_t n_envs, int64_t id_stride);
 
+/* ---------------------------------------------------------------- Q-network training (csrc/qtrain_kernels.hip) */
+/* ValueNet's minibatch step (algo/base.py:123-279, algo/q_learning.py) for the Q network above, f32, on the device:
+ * sample rows idx and (idx + 1) % n straight from the replay ring -> y = f32(f64(r) + ((1 - done) f64(q_target[argmax
+ * q_eval])) gamma) on the next rows -> loss = sum d^2 m / sum m with d = y - q_eval[a] on the current rows -> backward
+ * -> Adam (bias-corrected by the step count) -> target <- (1 - tau) target + tau eval.  Battle view 13 x 13 x 7,
+ * feature <= 256, n_action <= 32.
+ * The handle owns four blobs in the layout of mfx_qnet_blob_size -- the eval and target parameters and Adam's m and v
+ * -- and the step count.  Padding entries of every blob stay exactly zero.  The trained eval blob can go to
+ * mfx_qnet_set_weights device to device.
+ *   set_hyper        defaults: lr 1e-4, betas 0.9 / 0.999, eps 1e-8 (torch's Adam), tau 0.005, gamma 0.95; eps must be
+ *                    > 0 (an entry whose g, m and v are all zero divides by it and must stay zero)
+ *   set/get_state    `which` = MFX_QTRAIN_EVAL / TARGET / ADAM_M / ADAM_V; n_floats must be the blob size; a copy on
+ *                    `stream`.  Setting eval or target leaves the moments and the step count alone.
+ *   reset_optimizer  zeroes m, v and the step count
+ *   step_count       minibatches applied (host copy; exact after mfx_qtrain_error)
+ *   grads            the gradient of one minibatch in blob layout (padding zero) into d_grad_blob and (loss, mean
+ *                    q[a]) into d_stats (either may be null); no state changes; bit for bit the gradient run applies
+ *   run              n_batches minibatches in sequence, all enqueued by this one call: d_idx [n_batches][B] int64,
+ *                    d_stats [n_batches][2] (or null); nothing is read back, nothing synchronises
+ *   error            synchronises `stream`; *code = 0, or MFX_QTRAIN_BAD_INDEX (an idx outside [0, n)) /
+ *                    MFX_QTRAIN_BAD_ACTION (a ring action outside [0, n_action)) with the offending value in
+ *                    *bad_value, and clears it.  Indices and actions are checked on the device before any load
+ *                    that depends on them; from the bad minibatch on nothing is applied (state and step count
+ *                    unchanged, stats undefined) until this call has cleared the word.
+ * 1 <= B <= 4096, 1 <= n <= 2^31 - 1 (row offsets are 64-bit).  A null handle is refused.  Every sum has a fixed order: equal state and equal indices give bitwise equal results.  All
+ * launches go to `stream`; the ring columns must stay valid until they have run. */
+typedef struct mfx_qtrain_ring {          /* MemoryGroup's ring columns, rows [0, n) live */
+    const float *obs0;                    /* [rows][13 * 13 * 7] */
+    const float *feat0;                   /* [rows][feature] */
+    const int32_t *actions;               /* [rows] */
+    const float *rewards;                 /* [rows] */
+    const uint8_t *terminals;             /* [rows] 0 / 1 */
+    const uint8_t *masks;                 /* [rows] 0 / 1 */
+    const float *prob;                    /* [rows][n_action] (mean field), else null */
+} mfx_qtrain_ring;
+enum { MFX_QTRAIN_EVAL = 0, MFX_QTRAIN_TARGET = 1, MFX_QTRAIN_ADAM_M = 2, MFX_QTRAIN_ADAM_V = 3 };
+enum { MFX_QTRAIN_BAD_INDEX = 1, MFX_QTRAIN_BAD_ACTION = 2 };
+int mfx_qtrain_create(int feature, int n_action, int use_mf, void **handle);
+int mfx_qtrain_destroy(void *handle);
+int mfx_qtrain_set_hyper(void *handle, double lr, double beta1, double beta2, double eps, double tau, double gamma);
+int mfx_qtrain_set_state(void *handle, int which, const float *d_blob, size_t n_floats, void *stream);
+int mfx_qtrain_get_state(void *handle, int which, float *d_out, size_t n_floats, void *stream);
+int mfx_qtrain_reset_optimizer(void *handle, void *stream);
+int mfx_qtrain_step_count(void *handle, long long *t);
+int mfx_qtrain_grads(void *handle, const mfx_qtrain_ring *ring, long long n, const int64_t *d_idx, int B,
+                     float *d_grad_blob, float *d_stats, void *stream);
+int mfx_qtrain_run(void *handle, const mfx_qtrain_ring *ring, long long n, const int64_t *d_idx, int n_batches, int B,
+                   float *d_stats, void *stream);
+int mfx_qtrain_error(void *handle, int *code, long long *bad_value, void *stream);
+
 /* ---------------------------------------------------------------- measurement */
 /* The HBM write ceiling on this device, measured in-process beside the bench (csrc/diag_kernels.hip): total_bytes
  * of float4 stores over the device region [d_buf, d_buf + region_bytes), wrapping; shape 0..7: bit 0 = nontemporal

@@ -29,6 +29,7 @@ def weights_key(net, gen=0):
 class ValueNet:
     graph_train = True          # train() replays the minibatch step as a HIP graph (train_batches)
     act_precision = "f32"       # act_dev's HIP forward: "f32", or "bf16" operands (mfrl_amd.policy); training stays f32
+    _train_backend = "torch"    # train_batches: "torch" (the graph below), or "hip" (mfrl_amd.qtrain, csrc/qtrain_kernels.hip)
 
     def __init__(self, sess, env, handle, name, update_every=5, use_mf=False, learning_rate=1e-4, tau=0.005,
                  gamma=0.95):
@@ -56,6 +57,27 @@ class ValueNet:
         self._graph = None
         self._wgen = 0              # bumped after graph replays (they update the weights behind torch's back)
         self._hip_key = None
+
+    @property
+    def train_backend(self):
+        """The minibatch loop of train_batches: "torch" (the default: autograd + torch.optim.Adam, replayed as a HIP
+        graph) or "hip" (the hand-written training step, mfrl_amd.qtrain.QTrainHIP).  The two do not share optimizer
+        state: Adam's moments and step count of the "hip" backend live in its handle, torch's in self.optimizer, and
+        switching carries the weights over but neither backend's moments.  Setting "hip" on a model whose shapes the
+        kernels do not take (Battle view 13 x 13 x 7, feature <= 256, at most 32 actions) raises ValueError."""
+        return self._train_backend
+
+    @train_backend.setter
+    def train_backend(self, value):
+        if value not in ("torch", "hip"):
+            raise ValueError("train_backend %r (one of torch, hip)" % (value,))
+        if value == "hip":
+            from ..qtrain import supported
+            if not supported(self.view_space, self.feature_space, self.num_actions):
+                raise ValueError("train_backend 'hip' takes the Battle view (13, 13, 7), feature <= 256 and at most 32 "
+                                 "actions; this model has %r, %r, %d" % (self.view_space, self.feature_space,
+                                                                        self.num_actions))
+        self._train_backend = value
 
     @property
     def vars(self):
@@ -99,6 +121,8 @@ class ValueNet:
         (the warm-up graph capture needs); the losses are read back once at the end."""
         if batch_num <= 0:
             return
+        if self._train_backend == "hip":
+            return self._train_batches_hip(buf, batch_num, use_mean)
         n, B = buf.nb_entries, buf.batch_size
         idx = np.stack([np.random.choice(n, size=B) for _ in range(batch_num)]).astype(np.int64)
         nxt = (idx + 1) % n
@@ -130,6 +154,40 @@ class ValueNet:
             self._graph.replay()
             stats[i].copy_(self._s_out)
         self._wgen += 1
+        st = stats.cpu().numpy()
+        for i in range(0, batch_num, 50):
+            print("[*] LOSS:", float(st[i, 0]), "/ Q:", {"Eval-Q": np.round(float(st[i, 1]), 6)})
+
+    def _train_batches_hip(self, buf, batch_num, use_mean):
+        """train_batches on the hand-written training step: the same np.random.choice draws, then the whole sequential
+        minibatch loop enqueued by one call (mfx_qtrain_run) reading the ring rows in place; afterwards both blobs are
+        unpacked into the torch modules, so act_dev / act_rollout / save / vars / self_play_update see the new weights.
+        The nets are packed into the handle only when weights_key shows they moved since the handle last exported them
+        (self_play_update, load, a per-call train()).  Raises mfrl_amd.qtrain.QTrainError on a device error (a sample
+        index or a replay action out of range): the minibatches before it are applied, it and the later ones are not."""
+        assert bool(use_mean) == bool(self.use_mf), "train_batches: use_mean must match the model"
+        n, B = buf.nb_entries, buf.batch_size
+        idx = np.stack([np.random.choice(n, size=B) for _ in range(batch_num)]).astype(np.int64)
+        if getattr(self, "_qtrain", None) is None:
+            from ..qtrain import QTrainHIP
+            self._qtrain = QTrainHIP(self.view_space, self.feature_space, self.num_actions, self.use_mf, lr=self.lr,
+                                     tau=self.tau, gamma=self.gamma)
+            self._qtrain_key = None
+        tr = self._qtrain
+        tr.set_hyper(self.lr, tau=self.tau, gamma=self.gamma)      # the model's current values, as the torch path reads them
+        key = (weights_key(self.eval_net, self._wgen), weights_key(self.target_net, self._wgen))
+        if key != self._qtrain_key:
+            tr.load(self.eval_net, self.target_net)
+        cols = {"obs0": buf.obs0.data, "feat0": buf.feat0.data, "actions": buf.actions.data, "rewards": buf.rewards.data,
+                "terminals": buf.terminals.data, "masks": buf.masks.data, "prob": buf.prob.data if use_mean else None}
+        stats = tr.run(cols, n, torch.as_tensor(idx, device="cuda"))
+        code, bad = tr.error()                      # the one synchronisation of the round
+        tr.export(self.eval_net, self.target_net)
+        self._qtrain_key = (weights_key(self.eval_net, self._wgen), weights_key(self.target_net, self._wgen))
+        if code:
+            from ..qtrain import QTrainError
+            raise QTrainError("train_batches: device error %d (value %d); that minibatch and the later ones were not "
+                              "applied" % (code, bad))
         st = stats.cpu().numpy()
         for i in range(0, batch_num, 50):
             print("[*] LOSS:", float(st[i, 0]), "/ Q:", {"Eval-Q": np.round(float(st[i, 1]), 6)})

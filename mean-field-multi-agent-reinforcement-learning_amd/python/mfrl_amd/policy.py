@@ -103,6 +103,43 @@ def pack_qnet(net, feature, n_action, use_mf, layout=None):
     return blob
 
 
+@torch.no_grad()
+def unpack_qnet(blob, net, feature=None, n_action=None, use_mf=None, layout=None):
+    """The inverse of pack_qnet: the blob's 18 blocks copied in place (copy_) into the parameters of torch QNet `net`
+    (padding rows / columns dropped).  blob: float32 tensor on any device; the shapes default to the net's own."""
+    F = int(net.dense_emb.in_features if feature is None else feature)
+    A = int(net.q_value.out_features if n_action is None else n_action)
+    mf = bool(net.use_mf if use_mf is None else use_mf)
+    n, offsets = layout or blob_layout(F, A, mf)
+    assert blob.numel() == n, "unpack_qnet: %d floats, the layout has %d" % (blob.numel(), n)
+    Fp, Ap = (F + 3) & ~3, (A + 3) & ~3
+
+    def mat(k, rows, cols):
+        return blob[offsets[k]:offsets[k] + rows * cols].reshape(rows, cols)
+
+    def vec(k, p):
+        p.copy_(blob[offsets[k]:offsets[k] + p.numel()])
+
+    def dense(k, layer, rows=None, cols=None):
+        out_f, in_f = layer.weight.shape
+        layer.weight.copy_(mat(k, rows or in_f, cols or out_f)[:in_f, :out_f].t())
+        vec(k + 1, layer.bias)
+
+    net.conv1.weight.copy_(mat(0, 64, 32)[:63].reshape(3, 3, -1, 32).permute(3, 2, 0, 1))
+    vec(1, net.conv1.bias)
+    net.conv2.weight.copy_(mat(2, 288, 32).reshape(3, 3, 32, 32).permute(3, 2, 0, 1))
+    vec(3, net.conv2.bias)
+    dense(4, net.dense_obs)
+    dense(6, net.dense_emb, rows=Fp)
+    if mf:
+        dense(8, net.prob_emb, rows=Ap)
+        dense(10, net.dense_act_prob)
+    dense(12, net.dense2)
+    dense(14, net.dense_out)
+    dense(16, net.q_value, cols=32)
+    return net
+
+
 class QNetHIP:
     def __init__(self, view_space, feature_space, num_actions, use_mf=False, precision="f32"):
         if precision not in PRECISIONS:

@@ -3,6 +3,7 @@
     python -m mfrl_amd.train_battle --algo mfq --n_round 2000 --map_size 40 --max_steps 400
     python -m mfrl_amd.train_battle --algo mfq --envs 256 ...     # batched engine, all in HBM
     python -m mfrl_amd.train_battle --algo mfq --envs 256 --rollout ...   # the device rollout loop (mfq / il)
+    python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --train_backend hip ...   # + the HIP training step
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -48,7 +49,12 @@ def main(argv=None):
     parser.add_argument("--base_dir", type=str, default=os.getcwd())
     parser.add_argument("--rollout", action="store_true",
                         help="with --envs > 1: act, step and collect replay rows on the device rollout loop (mfq / il)")
+    parser.add_argument("--train_backend", type=str, choices=["torch", "hip"], default="torch",
+                        help="mfq / il: the minibatch loop on torch autograd (graph replay) or on the hand-written HIP "
+                             "training step (mfrl_amd.qtrain)")
     args = parser.parse_args(argv)
+    if args.train_backend == "hip" and args.algo not in ("mfq", "il"):
+        parser.error("--train_backend hip trains the Q network: --algo mfq or il")
     if args.rollout and args.envs <= 1:
         parser.error("--rollout needs the batched engine: --envs > 1")
     if args.rollout and args.algo not in ("mfq", "il"):
@@ -64,6 +70,9 @@ def main(argv=None):
     memory = min(80000 * args.envs, 2000000)
     models = [spawn_ai(args.algo, None, env, handles[0], args.algo + "-me", args.max_steps, memory_size=memory),
               spawn_ai(args.algo, None, env, handles[1], args.algo + "-opponent", args.max_steps, memory_size=memory)]
+    for m in models:
+        if args.train_backend != "torch":
+            m.train_backend = args.train_backend
     play_handle = play
     if args.envs > 1:
         from .battle import BattleBatch
