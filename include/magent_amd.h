@@ -236,7 +236,9 @@ int mfx_rollout_rows(const int32_t *d_counts, int E, int G, int g, int rowcap, i
 /* The actor-critic network of ActorCritic._create_network (algo/ac.py:48-98) / MFAC._create_network (:219-276)
  * and its act, tf.multinomial(log(policy)) (:43-46, :213-217), forward only, f32 MFMA
  * (csrc/acnet_kernels.hip); views of view_floats <= 4096 floats (flattened NHWC), features <= 256,
- * 2 <= n_action <= 32.  Weights: one float32 blob in the layout mfx_acnet_blob_size reports (19 offsets: wv bv
+ * 2 <= n_action <= 32.  The feature width picks one of two kernel forms: up to 36 floats h_emb is recomputed
+ * tile by tile from weights kept in LDS (two workgroups per CU), wider features hold it in registers (one).
+ * Weights: one float32 blob in the layout mfx_acnet_blob_size reports (19 offsets: wv bv
  * we be wd0 wd1 bd wp bp wval bval wep bep wdp bdp wvd bvd wvo bvo, every matrix [K][N] row-major, K padded to
  * 4; the 512-wide dense layer split by output halves).  The draw of row r of group g at step t is the first
  * action whose running f32 sum of the clipped policy exceeds u * (its f32 total), u = a 24-bit counter hash of

@@ -105,7 +105,13 @@ constexpr int kHeF = 36;
 #define MFX_ACNET_SKIP 0      // A/B builds only (make variant): 1 view layer, 2 dense layers, 4 policy layer, 8 h_emb skipped
 #endif
 constexpr size_t kAcnetLdsSmem = kQHeadSmem + (size_t)kHeF * kAH * 4;
-constexpr size_t kAcnetImgLdsSmem = kImgSmem + (size_t)kHeF * kAH * 4 + 3 * 1024 * 4;   // + the view ring: 80 KB
+// The imaged forms: the two chunk buffers, We (unused space when h_emb is held: that form is one workgroup per CU
+// either way), then the view ring at kAcnetRingOff floats.
+constexpr int kAcnetRingOff = 2 * kImgBuf + kHeF * kAH, kAcnetRing = 3 * 1024;
+constexpr size_t kAcnetImgLdsSmem = (size_t)(kAcnetRingOff + kAcnetRing) * 4;            // 80 KB
+// The dynamic LDS of k_acnet<.., kHeLds, kImg>: the one size the kernel's offsets and the launch share.
+constexpr size_t acnet_smem(bool he_lds, bool img) { return img ? kAcnetImgLdsSmem : he_lds ? kAcnetLdsSmem : kQHeadSmem; }
+static_assert(kAcnetImgLdsSmem >= kQHeadSmem, "the imaged form with h_emb held stages We through wg_gemm_t");
 
 // kImg: the layers run wg_gemm_i over the weight images (direct-to-LDS staging; made by set_weights), else
 // wg_gemm_t.  GEMM<MT, NCH, kZero>(block, image, K, v_at, acc) picks the form.
@@ -158,7 +164,7 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
         // the view rows through LDS: a ring of 3 chunks (64 agents x 16 floats each, after We), filled two chunks
         // ahead by direct-to-LDS loads -- instruction q of wave w: agent 4 (4 w + q) + lane / 16, float lane % 16
         // (columns past V read float V - 1: its weights are zero)
-        float* vring = bsm + 2 * kImgBuf + kHeF * kAH;
+        float* vring = bsm + kAcnetRingOff;
         const float* vsrc[4];
         // the packed order's chunk descriptors through the constant address space: scalar loads, each issued one
         // chunk before its use (a vector load here would wait, vmcnt being in order, for the chunk's image loads)
@@ -390,7 +396,7 @@ struct ACNetHandle {
     int vK = 0;                           // packed rows (a multiple of 16: pads are zero rows)
     int vKn = 0;                          // supported inputs
     int* vperm = nullptr;                 // [vK] view row of packed input p (-1: a zero pad row)
-    uint32_t* vdesc = nullptr;            // [(chunks + 2) * 8]
+    uint32_t* vdesc = nullptr;            // [(chunks + 3) * 8]
     float* vrows = nullptr;               // [vK][256]
     float* vimg = nullptr;
 };
@@ -543,7 +549,9 @@ MFX_API int mfx_acnet_set_input_support(void* handle, const uint8_t* mask, int n
     const int K = (int)chain.size(), nch = (K + 15) / 16;
     std::vector<int> orig((size_t)nch * 16, -1);                 // packed input -> view float (-1: a zero pad row)
     for (int i = 0; i < K; ++i) orig[16 * (i / 16) + 4 * (i % 4) + (i % 16) / 4] = chain[i];
-    std::vector<uint32_t> desc((size_t)(nch + 2) * 8, 0u);
+    // (k_acnet issues the view rows two chunks past the last one, and each issue loads the descriptor after its own:
+    // nch + 3 descriptors are read)
+    std::vector<uint32_t> desc((size_t)(nch + 3) * 8, 0u);
     for (int ch = 0; ch < nch + 2; ++ch) {
         int base = chain[K - 1];
         for (int j = 0; j < 16 && ch < nch; ++j)
@@ -578,7 +586,7 @@ MFX_API int mfx_acnet_input_support_size(void* handle, int* k) {
 }
 
 static int acnet_run(ACNetHandle* q, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
-                     const void* prob, int prob_f64, size_t prob_ld, QRowMap rm, int n, const int32_t* d_n,
+                     const float* prob, size_t prob_ld, QRowMap rm, int n, const int32_t* d_n,
                      float* policy, float* value, int32_t* act, uint32_t seed, uint32_t step, int group, hipStream_t st) {
     if (n <= 0) return 0;
     if (q->dev.use_mf && value && !prob) return fail("acnet: the mean-field value head needs prob");
@@ -587,29 +595,22 @@ static int acnet_run(ACNetHandle* q, const float* view, size_t view_ld, const fl
     const bool lds = q->dev.Fp <= kHeF;                             // (wider features: h_emb held in registers)
     const bool img = q->imaged;
     grid = std::min(grid, (lds ? 2 : 1) * device_cus());
-#define MFX_ACNET_LAUNCH1(PT, MF, LDS, IMG, PK, PB)                                                                     \
-    k_acnet<PT, MF, LDS, IMG, PK><<<grid, 256, IMG && LDS ? kAcnetImgLdsSmem : (LDS ? kAcnetLdsSmem : kQHeadSmem),     \
-                                    st>>>(q->dev, view, view_ld, feat, feat_ld, PB, prob_ld, rm, n, d_n, policy, value,   \
-                                          act, seed, step, group)
+#define MFX_ACNET_LAUNCH1(MF, LDS, IMG, PK)                                                                            \
+    k_acnet<float, MF, LDS, IMG, PK><<<grid, 256, acnet_smem(LDS, IMG), st>>>(                                         \
+        q->dev, view, view_ld, feat, feat_ld, prob, prob_ld, rm, n, d_n, policy, value, act, seed, step, group)
     // (the packed view order: the image path with h_emb in LDS -- the view-ring form -- and a support set)
-#define MFX_ACNET_LAUNCH(PT, MF, LDS, PB)                                                                              \
+#define MFX_ACNET_LAUNCH(MF, LDS)                                                                                      \
     do {                                                                                                              \
-        if (img && LDS && q->dev.vdesc) MFX_ACNET_LAUNCH1(PT, MF, LDS, true, LDS, PB);                               \
-        else if (img) MFX_ACNET_LAUNCH1(PT, MF, LDS, true, false, PB);                                                \
-        else MFX_ACNET_LAUNCH1(PT, MF, LDS, false, false, PB);                                                        \
+        if (img && LDS && q->dev.vdesc) MFX_ACNET_LAUNCH1(MF, LDS, true, LDS);                                       \
+        else if (img) MFX_ACNET_LAUNCH1(MF, LDS, true, false);                                                        \
+        else MFX_ACNET_LAUNCH1(MF, LDS, false, false);                                                                \
     } while (0)
-    const double* pd = static_cast<const double*>(prob);
-    const float* pf = static_cast<const float*>(prob);
     // (kMF selects only the value head: without value_out both forms compute the same policy, and the plain one
     // holds fewer registers)
-    if (!value) {
-        if (lds) MFX_ACNET_LAUNCH(float, false, true, pf); else MFX_ACNET_LAUNCH(float, false, false, pf);
-    } else if (q->dev.use_mf && prob_f64) {
-        if (lds) MFX_ACNET_LAUNCH(double, true, true, pd); else MFX_ACNET_LAUNCH(double, true, false, pd);
-    } else if (q->dev.use_mf) {
-        if (lds) MFX_ACNET_LAUNCH(float, true, true, pf); else MFX_ACNET_LAUNCH(float, true, false, pf);
+    if (value && q->dev.use_mf) {
+        if (lds) MFX_ACNET_LAUNCH(true, true); else MFX_ACNET_LAUNCH(true, false);
     } else {
-        if (lds) MFX_ACNET_LAUNCH(float, false, true, pf); else MFX_ACNET_LAUNCH(float, false, false, pf);
+        if (lds) MFX_ACNET_LAUNCH(false, true); else MFX_ACNET_LAUNCH(false, false);
     }
 #undef MFX_ACNET_LAUNCH
 #undef MFX_ACNET_LAUNCH1
@@ -624,7 +625,7 @@ MFX_API int mfx_acnet_forward(void* handle, const float* d_view, const float* d_
                               void* stream) {
     auto* q = static_cast<ACNetHandle*>(handle);
     QRowMap rm{nullptr, 1, 0, 0};
-    return acnet_run(q, d_view, q->dev.V, d_feat, q->dev.F, d_prob, 0, q->dev.A, rm, n, nullptr, d_policy, d_value,
+    return acnet_run(q, d_view, q->dev.V, d_feat, q->dev.F, d_prob, q->dev.A, rm, n, nullptr, d_policy, d_value,
                      d_act, seed, step, 0, (hipStream_t)stream);
 }
 
@@ -637,7 +638,7 @@ MFX_API int mfx_acnet_act_rollout(void* handle, const float* d_view, const float
     hipStream_t st = (hipStream_t)stream;
     MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
     QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap};
-    return acnet_run(q, d_view, q->dev.V, d_feat, q->dev.F, nullptr, 0, 0, rm, E * rowcap, d_total, nullptr, nullptr,
+    return acnet_run(q, d_view, q->dev.V, d_feat, q->dev.F, nullptr, 0, rm, E * rowcap, d_total, nullptr, nullptr,
                      d_act, seed, step, g, st);
 }
 

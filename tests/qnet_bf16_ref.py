@@ -70,8 +70,9 @@ def fixture_rows():
     return view, feat, prob
 
 
-def net(use_mf, seed):
-    """A torch QNet on the CPU, initialised as tests/test_policy_gpu.py::_net: Glorot + 0.05 randn on every parameter."""
+def net(use_mf, seed, F=F, A=A):
+    """A torch QNet on the CPU, initialised as tests/test_policy_gpu.py::_net: Glorot + 0.05 randn on every parameter
+    (F features, A actions: the Battle shape unless given)."""
     import torch
     from mfrl_amd.algo.nets import QNet
     torch.manual_seed(seed)
@@ -82,23 +83,25 @@ def net(use_mf, seed):
     return m
 
 
-def packed(m, use_mf):
+def packed(m, use_mf, F=F, A=A):
     """(blob float32 numpy, offsets) of net m."""
     from mfrl_amd.policy import blob_layout, pack_qnet
     layout = blob_layout(F, A, use_mf)
     return pack_qnet(m, F, A, use_mf, layout).cpu().numpy(), layout[1]
 
 
-def quantisation(m, use_mf, view, feat, prob):
+def quantisation(m, use_mf, view, feat, prob, F=F, A=A):
     """(q_exact, q_bf16, e_q, scale) of net m on the rows: the float64 unrounded forward, the bf16 reference, the
     reference's quantisation error max |q_bf16 - q_exact| and the Q scale max(1, max |q_exact|)."""
-    blob, off = packed(m, use_mf)
+    blob, off = packed(m, use_mf, F, A)
     exact = qnet_ref.forward(blob.astype(np.float64), off, F, A, use_mf, view, feat, prob if use_mf else None)
     quant = forward(blob, off, F, A, use_mf, view, feat, prob if use_mf else None)
     return exact, quant, float(np.abs(quant - exact).max()), max(1.0, float(np.abs(exact).max()))
 
 
 def clear_rows(exact, e_q):
-    """Rows whose top-two exact Q values are more than 2 e_q apart."""
+    """Rows whose top-two exact Q values are more than 2 e_q apart (one action: every row)."""
+    if exact.shape[1] < 2:
+        return np.ones(len(exact), dtype=bool)
     s = np.sort(exact, axis=1)
     return (s[:, -1] - s[:, -2]) > 2.0 * e_q

@@ -141,9 +141,16 @@ def adam(p, tgt, m, v, g, t, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, tau=0.00
 
 
 # ------------------------------------------------------------------------------------------------- shared inputs
-def ring(seed):
-    """The ring the tests share: the 256 fixture rows, n = 200 live; columns from RandomState(100 + seed)."""
+def ring(seed, F=F, A=A):
+    """The ring the tests share: the 256 fixture rows, n = 200 live; columns from RandomState(100 + seed).  Other
+    widths than the fixture's (F = 34, A = 21): the features uniform in [0, 1), the mean actions Dirichlet(1), from
+    RandomState(200 + seed) -- the columns' stream stays the default shape's."""
     view, feat, prob = qb.fixture_rows()
+    wide = np.random.RandomState(200 + seed)
+    if F != qb.F:
+        feat = wide.rand(RING_ROWS, F).astype(np.float32)
+    if A != qb.A:
+        prob = wide.dirichlet(np.ones(A), RING_ROWS).astype(np.float32)
     rng = np.random.RandomState(100 + seed)
     return {"obs": view, "feat": feat, "prob": prob,
             "act": rng.randint(A, size=RING_ROWS).astype(np.int32),
@@ -161,9 +168,9 @@ def index_list(seed, B, n=N_RING):
     return idx
 
 
-def nets(use_mf, seed):
+def nets(use_mf, seed, F=F, A=A):
     """(eval, target) torch QNets on the CPU: qnet_bf16_ref.net(use_mf, seed) and net(use_mf, seed + 100)."""
-    return qb.net(use_mf, seed), qb.net(use_mf, seed + 100)
+    return qb.net(use_mf, seed, F, A), qb.net(use_mf, seed + 100, F, A)
 
 
 def pack64(named, F, A, use_mf, offsets, n):
