@@ -321,6 +321,26 @@ int mfx_collect_end(const mfx_collect_src *src, const mfx_collect_dst *dst, cons
 /* (episode * n_envs + env) * id_stride + id: injective over env < n_envs, episode >= 0, id < id_stride (host) */
 int64_t mfx_collect_key(int64_t env, int64_t episode, int64_t id, int64_t n_envs, int64_t id_stride);
 
+/* Episode chains for the actor-critic models, whose returns run backwards along each agent's rows of one episode.
+ *   mfx_collect_end_linked  mfx_collect_end, and in the same launch two more columns of step row r = n + k:
+ *                      d_prev[r] = the row of the same key one step earlier, or -1; d_tail[r] = 1 while r is the
+ *                      last row of its key (the predecessor's tail is cleared).  d_last: n_envs * id_stride int64,
+ *                      [env * id_stride + id] = the newest row of that id, -1 when empty (mfx_collect_links_reset
+ *                      before a session's first step); an entry left by an earlier episode fails the key
+ *                      comparison.  A live id occurs once per env and step: no atomics.  The capacity rule holds:
+ *                      a step that does not fit touches neither d_last, d_prev nor d_tail.
+ *   mfx_chain_returns  in place on d_rew: for tail i, keep = d_value[i]; along r = d_tails[i], d_prev[r], ... to
+ *                      -1: keep = keep * gamma + d_rew[r]; d_rew[r] = keep, in mfx_mfac_returns' two arithmetic
+ *                      forms (numpy1).  Rows are step-major: a predecessor is below its row.  A tail outside
+ *                      [0, n_rows) or a predecessor outside [0, its row) ends that walk before any further store
+ *                      and the call returns -1 (it synchronises `stream` to report it). */
+int mfx_collect_end_linked(const mfx_collect_src *src, const mfx_collect_dst *dst, const int32_t *d_rows,
+                           const int32_t *d_total, int64_t *d_state, int64_t id_stride, int64_t *d_last,
+                           int64_t *d_prev, uint8_t *d_tail, void *stream);
+int mfx_collect_links_reset(int64_t *d_last, int64_t n, void *stream);
+int mfx_chain_returns(float *d_rew, const int64_t *d_prev, const int64_t *d_tails, const float *d_value,
+                      int64_t n_tails, int64_t n_rows, double gamma, int numpy1, void *stream);
+
 /* ---------------------------------------------------------------- Q-network training (csrc/qtrain_kernels.hip) */
 /* ValueNet's minibatch step (algo/base.py:123-279, algo/q_learning.py) for the Q network above, f32, on the device:
  * sample rows idx and (idx + 1) % n straight from the replay ring -> y = f32(f64(r) + ((1 - done) f64(q_target[argmax

@@ -16,6 +16,11 @@
 // check n + count against the destination capacity before any store: a step that does not fit writes nothing, sets
 // bit 0 of the error word (sticky) and leaves n where it was.
 //
+// For the actor-critic models (EpisodesBuffer rows: algo/ac.py train_rollout) mfx_collect_end_linked also records,
+// in the same launch, which row precedes each row in its agent's episode (prev) and which rows end a chain so far
+// (tail); mfx_chain_returns then turns the reward column into discounted returns in place by walking those chains,
+// so the step-major rows are never sorted or regrouped.
+//
 // The view move is the HBM-bound part (4,732 B read + written per row, up to 40 GB per step at 256x256 x 2048 envs)
 // and follows k_rows_pipe (replay_kernels.hip): one wave per row, 16-B units at the rows' dword alignment, two rows in
 // flight per wave -- row k + W's loads are issued before row k's stores --, the list entry through a scalar load (the
@@ -123,11 +128,21 @@ __global__ void __launch_bounds__(256) k_collect_begin(mfx_collect_src s, mfx_co
     }
 }
 
-// One lane per list entry: reward, terminal and key of step row n + k.
+// The link columns of a linked collection (mfx_collect_end_linked); all null in the unlinked kernel.
+struct CollectLinks {
+    int64_t* last;             // [n_envs * id_stride]: the newest row of (env, id), -1 when empty
+    int64_t* prev;             // [capacity]
+    uint8_t* tail;             // [capacity]
+};
+
+// One lane per list entry: reward, terminal and key of step row n + k.  kLink: also the row's place in its agent's
+// episode chain -- prev[r] = the row of the same key one step earlier (or -1), tail[r] = 1 and the predecessor's
+// tail = 0 --, found through the table `last` of the newest row per (env, id).
+template <bool kLink>
 __global__ void __launch_bounds__(256) k_collect_end(mfx_collect_src s, mfx_collect_dst d,
                                                      const int32_t* __restrict__ rows,
                                                      const int32_t* __restrict__ total, int64_t* state,
-                                                     int64_t id_stride) {
+                                                     int64_t id_stride, CollectLinks lk) {
     const int count = *total;
     const int64_t n = state[0];
     if (n + count > d.capacity) {
@@ -142,8 +157,63 @@ __global__ void __launch_bounds__(256) k_collect_end(mfx_collect_src s, mfx_coll
         if (id < 0 || id >= id_stride) collect_flag(state, 2ull);      // the key would not be injective
         d.rew[n + k] = s.rewards[slot];
         d.term[n + k] = (uint8_t)(s.alive[slot] == 0);
-        d.key[n + k] = collect_key(e, d.key[n + k], id, s.n_envs, id_stride);
+        const int64_t key = collect_key(e, d.key[n + k], id, s.n_envs, id_stride);
+        d.key[n + k] = key;
+        if constexpr (kLink) {
+            // No atomic and no race: a live id occurs once per env and step, so this lane is the only one of the
+            // launch that touches last[e][id], and the only one that clears tail[p] (p is that slot's row of an
+            // earlier step, below n; every store of this step is at or above n).  A stale entry -- the id's row of
+            // an earlier episode -- fails the key comparison, the episode number being part of the key.  An id the
+            // check above flagged has no table entry and starts a chain of its own.
+            int64_t p = -1;
+            if (id >= 0 && id < id_stride) {
+                int64_t* slot_last = lk.last + (size_t)e * id_stride + id;
+                p = *slot_last;
+                if (p < 0 || p >= n || d.key[p] != key) p = -1;
+                *slot_last = n + k;
+            }
+            if (p >= 0) lk.tail[p] = 0;
+            lk.prev[n + k] = p;
+            lk.tail[n + k] = 1;
+        }
     }
+}
+
+__global__ void __launch_bounds__(256) k_fill_i64(int64_t* __restrict__ p, int64_t n, int64_t v) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        p[i] = v;
+}
+
+// Discounted returns in place on step-major rows (mfx_chain_returns): one lane per chain, from its tail row back
+// along prev, keep = keep * gamma + rew[r]; rew[r] = keep -- k_mfac_returns' recursion (mf_kernels.hip) and its two
+// arithmetic forms (numpy1: float64 keep; else float32 keep and gamma; -ffp-contract=off keeps the multiply and the
+// add apart), over a linked list instead of a contiguous run.  Latency-bound like it: every step of a chain is a
+// load that depends on the one before.  Rows are step-major, so a predecessor lies strictly below its row: a tail
+// outside [0, n_rows) or a prev that is neither -1 nor in [0, r) ends the walk there (nothing is stored past it, and
+// no walk can cycle) and sets err[0] = 1, err[1] = an offending index.
+__device__ int64_t g_chain_err[2];       // zero at load; read, and cleared when set, by mfx_chain_returns
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_chain_returns(float* __restrict__ rew, const int64_t* __restrict__ prev,
+                                                       const int64_t* __restrict__ tails,
+                                                       const float* __restrict__ value, int64_t n_tails,
+                                                       int64_t n_rows, T gamma, int64_t* err) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tails) return;
+    T keep = (T)value[i];
+    int64_t r = tails[i], above = n_rows;
+    do {
+        if (r < 0 || r >= above) {
+            err[1] = r;                              // (any offender: lanes may race here, each with a bad index)
+            err[0] = 1;
+            return;
+        }
+        const T t = keep * gamma;
+        keep = t + (T)rew[r];
+        rew[r] = (float)keep;
+        above = r;
+        r = prev[r];
+    } while (r != -1);
 }
 
 // Behind the row writes of its step on the same stream: n += count when the step fitted.
@@ -212,10 +282,62 @@ MFX_API int mfx_collect_end(const mfx_collect_src* src, const mfx_collect_dst* d
     if (id_stride < 1) return fail("collect_end: id stride %lld", (long long)id_stride);
     hipStream_t st = (hipStream_t)stream;
     const int64_t wgs = ((int64_t)src->n_envs * src->rowcap + 255) / 256, cap = (int64_t)device_cus() * 8;
-    k_collect_end<<<(int)(wgs < cap ? wgs : cap), 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state, id_stride);
+    k_collect_end<false><<<(int)(wgs < cap ? wgs : cap), 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state, id_stride,
+                                                                       CollectLinks{nullptr, nullptr, nullptr});
     MFX_HIP(hipGetLastError());
     k_collect_advance<<<1, 1, 0, st>>>(d_total, d_state, dst->capacity);
     MFX_HIP(hipGetLastError());
+    return 0;
+}
+
+MFX_API int mfx_collect_end_linked(const mfx_collect_src* src, const mfx_collect_dst* dst, const int32_t* d_rows,
+                                   const int32_t* d_total, int64_t* d_state, int64_t id_stride, int64_t* d_last,
+                                   int64_t* d_prev, uint8_t* d_tail, void* stream) {
+    MFX_CHECK(collect_shape(src, dst, d_rows, d_total, d_state));
+    if (id_stride < 1) return fail("collect_end_linked: id stride %lld", (long long)id_stride);
+    if (!d_last || !d_prev || !d_tail) return fail("collect_end_linked: a link column is missing");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t wgs = ((int64_t)src->n_envs * src->rowcap + 255) / 256, cap = (int64_t)device_cus() * 8;
+    k_collect_end<true><<<(int)(wgs < cap ? wgs : cap), 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state, id_stride,
+                                                                      CollectLinks{d_last, d_prev, d_tail});
+    MFX_HIP(hipGetLastError());
+    k_collect_advance<<<1, 1, 0, st>>>(d_total, d_state, dst->capacity);
+    MFX_HIP(hipGetLastError());
+    return 0;
+}
+
+MFX_API int mfx_collect_links_reset(int64_t* d_last, int64_t n, void* stream) {
+    if (n < 0 || (n > 0 && !d_last)) return fail("collect_links_reset: bad argument");
+    if (n == 0) return 0;
+    const int64_t wgs = (n + 255) / 256, cap = (int64_t)device_cus() * 8;
+    k_fill_i64<<<(int)(wgs < cap ? wgs : cap), 256, 0, (hipStream_t)stream>>>(d_last, n, -1);
+    MFX_HIP(hipGetLastError());
+    return 0;
+}
+
+MFX_API int mfx_chain_returns(float* d_rew, const int64_t* d_prev, const int64_t* d_tails, const float* d_value,
+                              int64_t n_tails, int64_t n_rows, double gamma, int numpy1, void* stream) {
+    if (n_tails < 0 || n_rows < 0) return fail("chain_returns: n_tails and n_rows must be >= 0");
+    if (n_tails == 0) return 0;
+    if (!d_rew || !d_prev || !d_tails || !d_value) return fail("chain_returns: null argument");
+    if (n_tails > n_rows) return fail("chain_returns: %lld tails for %lld rows", (long long)n_tails, (long long)n_rows);
+    hipStream_t st = (hipStream_t)stream;
+    int64_t* err = nullptr;
+    MFX_HIP(hipGetSymbolAddress((void**)&err, HIP_SYMBOL(g_chain_err)));
+    const unsigned grid = (unsigned)((n_tails + 255) / 256);
+    if (numpy1) k_chain_returns<double><<<grid, 256, 0, st>>>(d_rew, d_prev, d_tails, d_value, n_tails, n_rows, gamma, err);
+    else k_chain_returns<float><<<grid, 256, 0, st>>>(d_rew, d_prev, d_tails, d_value, n_tails, n_rows, (float)gamma, err);
+    MFX_HIP(hipGetLastError());
+    int64_t h[2] = {0, 0};
+    MFX_HIP(hipMemcpyAsync(h, err, sizeof h, hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    if (h[0]) {
+        const int64_t z[2] = {0, 0};
+        MFX_HIP(hipMemcpyAsync(err, z, sizeof z, hipMemcpyHostToDevice, st));
+        MFX_HIP(hipStreamSynchronize(st));
+        return fail("chain_returns: row index %lld is outside its chain's rows (tails in [0, %lld), a predecessor in "
+                    "[0, its row))", (long long)h[1], (long long)n_rows);
+    }
     return 0;
 }
 

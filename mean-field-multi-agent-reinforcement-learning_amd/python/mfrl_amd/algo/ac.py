@@ -6,6 +6,11 @@ only when training changed them); train builds one batch from the
 episode buffer, bootstraps every agent's sequence from the value of its last row, and runs the
 discounted-return recursion keep = keep * gamma + r on the device (HIP kernel mfx_mfac_returns,
 algo/ac.py:305-320), then one Adam step on pg + value_coef * vf + ent_coef * neg_entropy.
+
+act_rollout / train_rollout are the same two on the device rollout loop: the actions go straight into a
+BattleBatch's action buffer, and training runs on the rows a linked RolloutCollector left in the episode buffer,
+in place -- the returns walk each agent's chain of rows (HIP kernel mfx_chain_returns) instead of regrouping the
+rows per agent, and no np.random is drawn.
 """
 import os
 import zlib
@@ -84,15 +89,18 @@ class ActorCritic:
     def act(self, **kwargs):
         return self.act_dev(**kwargs).cpu().numpy().astype(np.int32)
 
-    def losses(self, view, feature, action, reward, prob=None):
+    def losses(self, view, feature, action, reward, prob=None, total_rows=None):
+        """total_rows: these rows are one chunk of that many (train_rollout) -- every mean becomes the chunk's sum
+        over total_rows, so that the chunks' losses add up to the means over all rows."""
+        mean = torch.mean if total_rows is None else (lambda x: torch.sum(x) / total_rows)
         policy, value = self.net(view, feature, prob)
         action_mask = torch.nn.functional.one_hot(action.long(), self.num_actions).float()
         advantage = (reward - value).detach()
         log_policy = torch.log(policy + 1e-6)
         log_prob = torch.sum(log_policy * action_mask, dim=1)
-        pg_loss = -torch.mean(advantage * log_prob)
-        vf_loss = self.value_coef * torch.mean(torch.square(reward - value))
-        neg_entropy = self.ent_coef * torch.mean(torch.sum(policy * log_policy, dim=1))
+        pg_loss = -mean(advantage * log_prob)
+        vf_loss = self.value_coef * mean(torch.square(reward - value))
+        neg_entropy = self.ent_coef * mean(torch.sum(policy * log_policy, dim=1))
         return pg_loss, vf_loss, neg_entropy, value
 
     def train(self):
@@ -121,6 +129,95 @@ class ActorCritic:
         self.optimizer.step()
         print("[*] PG_LOSS:", np.round(pg_loss.item(), 6), "/ VF_LOSS:", np.round(vf_loss.item(), 6),
               "/ ENT_LOSS:", np.round(ent_loss.item(), 6), "/ VALUE:", state_value.mean().item())
+
+    # ---- the device rollout loop (play.play_rollout_episodes)
+    @torch.no_grad()
+    def act_rollout(self, eng, group):
+        """Sampled actions of group `group` of a BattleBatch's rollout from its observation buffers into its action
+        buffer (mfrl_amd.policy.ACNetHIP.act_rollout) with the current weights and the draw of act_dev (self.seed,
+        the act count); nothing is read back.  The weights are uploaded on the caller's current stream: when they
+        moved and the engine sits on another stream, the engine's stream waits for the upload."""
+        if not self._hip_ok():
+            raise ValueError("act_rollout: the HIP forward takes 2..32 actions, views of at most 4096 floats and at "
+                             "most 256 features")
+        before = self._hip_key
+        hip = self._hip_net()
+        if self._hip_key != before and eng.stream_handle() != torch.cuda.current_stream().cuda_stream:
+            eng.torch_stream().wait_stream(torch.cuda.current_stream())
+        self._draws += 1
+        hip.act_rollout(eng, group, seed=self.seed, step=self._draws)
+
+    def rollout_collector(self, eng, group=0):
+        """The RolloutCollector of this model's EpisodesBuffer on `eng` (linked rows; made once and kept while
+        the engine and the buffer stay the same)."""
+        from ..replay import RolloutCollector
+        rows = self.replay_buffer.prepare(self.view_space, self.feature_space, self.num_actions if self._use_mf else 1)
+        col = getattr(self, "_rollout_collector", None)
+        if col is None or col.eng is not eng or col.mg is not self.replay_buffer or col.group != group:
+            col = self._rollout_collector = RolloutCollector(eng, self.replay_buffer, group)
+        assert col.mg._rows is rows
+        return col
+
+    # rows per autograd graph of train_rollout: the activations kept for backward are about 7 KB per row (the view
+    # and its 256-wide layer, the 512-wide dense layer twice, the heads), so 65,536 rows hold about 0.5 GB -- large
+    # enough that the launches of a chunk are not the cost, small against HBM at any round size.  Nothing depends
+    # on the value beyond the float summation order of the gradient.
+    ROLLOUT_CHUNK_ROWS = 65536
+
+    def train_rollout(self, chunk_rows=None, step=True):
+        """train() for rows collected by this model's RolloutCollector, where they lie.  finish() the collector;
+        tails = the rows that end a chain (the host synchronisation the path needs: their number; chain_returns
+        then waits once more, for its error word, with nothing left to overlap); the bootstrap value of
+        every chain from its tail row on k_acnet, as train() takes it from every agent's last row; the returns in
+        place on the reward column along the chains (replay.chain_returns); then the losses of train() over the
+        rows in contiguous chunks of at most chunk_rows -- each chunk's sums divided by the total row count, so the
+        chunks' gradients add up to the gradient of the means over all rows -- and one Adam step.  The losses are
+        means over rows, so the step-major order changes their float summation order and nothing else.
+        step=False: no Adam step; returns the gradients (one tensor per parameter, None where there is none).
+        Afterwards the rows are cleared; the buffer and its storage are kept."""
+        from .. import replay
+        col = getattr(self, "_rollout_collector", None)
+        if col is None or col.mg is not self.replay_buffer:
+            raise RuntimeError("train_rollout: no rows were collected (rollout_collector() / play_rollout_episodes)")
+        col.finish()
+        rows = self.replay_buffer._rows
+        n = rows.n
+        if n == 0:
+            return None
+        chunk = int(chunk_rows or self.ROLLOUT_CHUNK_ROWS)
+        assert chunk >= 1
+        c = rows.cols
+        prob = c["prob"] if self._use_mf else None
+        with torch.cuda.stream(col.eng.torch_stream()), torch.no_grad():
+            tails = c["tail"][:n].nonzero().reshape(-1)
+            p_t = prob[tails] if prob is not None else None
+            if self._hip_ok():
+                _, keep, _ = self._hip_net().forward(c["obs"][tails], c["feat"][tails], p_t, want_policy=False,
+                                                     want_value=True, want_act=False)
+            else:
+                _, keep = self.net(c["obs"][tails], c["feat"][tails], p_t)
+            replay.chain_returns(c["rew"][:n], c["prev"], tails, keep.float().reshape(-1), self.gamma)
+        torch.cuda.current_stream().wait_stream(col.eng.torch_stream())
+        self.optimizer.zero_grad(set_to_none=True)
+        sums = torch.zeros(4, dtype=torch.float64, device="cuda")
+        for a in range(0, n, chunk):
+            b = min(a + chunk, n)
+            pg, vf, ent, value = self.losses(c["obs"][a:b], c["feat"][a:b], c["act"][a:b], c["rew"][a:b],
+                                             prob[a:b] if prob is not None else None, total_rows=n)
+            (pg + vf + ent).backward()
+            sums += torch.stack([pg.detach(), vf.detach(), ent.detach(), value.detach().sum() / n]).double()
+        col.eng.torch_stream().wait_stream(torch.cuda.current_stream())     # the next round writes these rows
+        grads = None
+        if step:
+            self.optimizer.step()
+        else:
+            grads = [None if p.grad is None else p.grad.detach().clone() for p in self.net.parameters()]
+            self.optimizer.zero_grad(set_to_none=True)
+        self.replay_buffer.clear()
+        pg, vf, ent, val = sums.tolist()
+        print("[*] PG_LOSS:", np.round(pg, 6), "/ VF_LOSS:", np.round(vf, 6), "/ ENT_LOSS:", np.round(ent, 6),
+              "/ VALUE:", val, "({} rows, {} chains)".format(n, len(tails)))
+        return grads
 
     def save(self, dir_path, step=0):
         os.makedirs(dir_path, exist_ok=True)

@@ -8,6 +8,8 @@
   rows 1-2).  Agent keys in the buffers are env * cap + id.
 * play_rollout: a round on the device rollout loop (act_rollout + rollout_policy_step, no host round trip
   per step), the replay rows collected by mfrl_amd.replay.RolloutCollector (DQN / MFQ).
+* play_rollout_episodes: the same round for ActorCritic / MFAC -- the rows go into the model's EpisodesBuffer with
+  their episode chains (the collector's linked path) and train_rollout() trains on them in place.
 """
 import math
 import random
@@ -218,7 +220,45 @@ def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=
             raise TypeError("play_rollout: %s has no device rollout forward (DQN / MFQ only)" % type(m).__name__)
     if train and not isinstance(getattr(models[0], "replay_buffer", None), MemoryGroup):
         raise TypeError("play_rollout: %s does not train from a MemoryGroup (DQN / MFQ only; EpisodesBuffer "
-                        "consumes host randomness per push)" % type(models[0]).__name__)
+                        "consumes host randomness per push -- play_rollout_episodes trains AC / MFAC)"
+                        % type(models[0]).__name__)
+
+    def collector():
+        col = getattr(models[0], "_rollout_collector", None)
+        if col is None or col.eng is not eng or col.mg is not models[0].replay_buffer:
+            col = models[0]._rollout_collector = RolloutCollector(eng, models[0].replay_buffer, 0)
+        return col
+
+    return _rollout_round("play_rollout", eng, n_round, map_size, max_steps, models, eps, train, left_id, collector,
+                          models[0].train)
+
+
+def play_rollout_episodes(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, train=False, left_id=None):
+    """play_rollout for the actor-critic models (ActorCritic, MFAC: act_rollout and an EpisodesBuffer): the same
+    round -- max_steps steps of every env on the device rollout loop, an env that ends early restarting inside the
+    loop, the statistics read once at the end from the rollout's buffers -- with group 0's rows collected into
+    models[0]'s EpisodesBuffer by a linked RolloutCollector and trained by models[0].train_rollout().
+
+    An agent's sequence ends at its death, at the end of its episode (done or the step cap) or at the end of the
+    round, and every sequence is bootstrapped from the value of its last row, as the reference's loop and
+    ActorCritic.train do for every agent.  No np.random is consumed: the reference's per-push permutation only orders
+    the agents inside the batch, which changes the float summation order of the loss means and nothing else.
+    A MemoryGroup model (DQN / MFQ) is refused: play_rollout is its loop."""
+    from .tools import EpisodesBuffer
+    for m in models[:2]:
+        if not hasattr(m, "act_rollout"):
+            raise TypeError("play_rollout_episodes: %s has no device rollout forward" % type(m).__name__)
+    if not (isinstance(getattr(models[0], "replay_buffer", None), EpisodesBuffer) and hasattr(models[0], "train_rollout")):
+        raise TypeError("play_rollout_episodes: %s does not train from an EpisodesBuffer (AC / MFAC only; play_rollout "
+                        "trains DQN / MFQ)" % type(models[0]).__name__)
+    return _rollout_round("play_rollout_episodes", eng, n_round, map_size, max_steps, models, eps, train, left_id,
+                          lambda: models[0].rollout_collector(eng, 0), models[0].train_rollout)
+
+
+def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, left_id, collector, train_fn):
+    """The round of play_rollout / play_rollout_episodes: collector() gives group 0's RolloutCollector, train_fn()
+    trains models[0] on what it collected."""
+    E, G = eng.n_envs, 2
     left, right = block_positions(map_size)
     left_id = random.randint(0, 1) if left_id is None else left_id
     placement = [None, None]
@@ -226,13 +266,9 @@ def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=
     eng.reset()
     eng.rollout_init(placement, max_steps=max_steps, eps=0.0, seed=n_round, stagger=False)
     if eng.rollout_policy_path() is None:
-        raise RuntimeError("play_rollout: this rollout plan takes no learned policy (MFX_ROLLOUT_PIPE=1)")
+        raise RuntimeError("%s: this rollout plan takes no learned policy (MFX_ROLLOUT_PIPE=1)" % name)
     eng.rollout_policy_observe()
-    col = None
-    if train:
-        col = getattr(models[0], "_rollout_collector", None)
-        if col is None or col.eng is not eng or col.mg is not models[0].replay_buffer:
-            col = models[0]._rollout_collector = RolloutCollector(eng, models[0].replay_buffer, 0)
+    col = collector() if train else None
     max_nums = [len(placement[g]) * E for g in range(G)]
     print("\n\n[*] ROUND #{0}, EPS: {1:.2f} NUMBER: {2} ({3} envs, device rollout)".format(n_round, eps, max_nums, E))
     t_play = time.time()
@@ -260,7 +296,7 @@ def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=
     mean_rewards = [total_rewards[g] / max(agent_steps / G, 1.0) for g in range(G)]
     t_train = time.time()
     if train:
-        models[0].train()
+        train_fn()
         torch.cuda.synchronize()
     print("[TIME] play {} steps x {} envs: {:.2f} s ({:.3g} agent-steps/s incl. policy forward); train {:.2f} s"
           .format(max_steps, E, t_play, agent_steps / max(t_play, 1e-9), time.time() - t_train))

@@ -106,10 +106,13 @@ class MetaBuffer:
 
 
 class _StepRows:
-    """Rows pushed during an episode, step-major, on the device (grown geometrically)."""
+    """Rows pushed during an episode, step-major, on the device (grown geometrically).  links: two more columns,
+    written by the rollout collector's linked path only (mfrl_amd.replay.RolloutCollector) -- prev, the row of the
+    same agent's previous step in the same episode or -1, and tail, whether the row is its agent's last."""
 
-    def __init__(self, obs_shape, feat_shape, act_n, use_mean, device="cuda"):
+    def __init__(self, obs_shape, feat_shape, act_n, use_mean, device="cuda", links=False):
         self.obs_shape, self.feat_shape, self.act_n, self.use_mean = tuple(obs_shape), tuple(feat_shape), act_n, use_mean
+        self.links = bool(links)
         self.device = device
         self.n = 0
         self.cap = 0
@@ -126,7 +129,10 @@ class _StepRows:
                 "act": ((), torch.int32), "rew": ((), torch.float32), "term": ((), torch.bool)}
         if self.use_mean:
             spec["prob"] = ((self.act_n,), torch.float32)
-        new = {k: torch.empty((cap,) + s, dtype=d, device=self.device) for k, (s, d) in spec.items()}
+        if self.links:
+            spec["prev"] = ((), torch.int64)
+            spec["tail"] = ((), torch.bool)
+        new ={k: torch.empty((cap,) + s, dtype=d, device=self.device) for k, (s, d) in spec.items()}
         if live:
             keys = list(self.cols)
             _move([new[k] for k in keys], [self.cols[k] for k in keys], n=live)
@@ -288,6 +294,23 @@ class EpisodesBuffer:
 
     def reset(self):
         self._rows = None
+
+    def prepare(self, obs_shape, feat_shape, act_n=1):
+        """Create the step rows ahead of the first push, with the link columns, for a
+        mfrl_amd.replay.RolloutCollector (which has no first push to take the shapes from); returns them.  Rows of
+        the same shapes that already have link columns are kept."""
+        r = self._rows
+        if (r is None or not r.links or r.obs_shape != tuple(obs_shape) or r.feat_shape != tuple(feat_shape)
+                or r.act_n != act_n):
+            if r is not None and r.n:
+                raise ValueError("EpisodesBuffer.prepare: %d pushed rows of another layout are present" % r.n)
+            self._rows = _StepRows(obs_shape, feat_shape, act_n, self.use_mean, self.device, links=True)
+        return self._rows
+
+    def clear(self):
+        """Empty the rows; the storage is kept (reset() drops it)."""
+        if self._rows is not None:
+            self._rows.clear()
 
     def batch(self):
         """(rows dict gathered per agent, counts per agent) in dict order, or None if empty."""

@@ -4,6 +4,7 @@ is one launch that gathers whole rows of all its columns.  CUDA tensors only; a 
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import check, lib
@@ -86,18 +87,32 @@ class RolloutCollector:
     the worst case of one more step (E * rowcap rows past a running upper bound of the count; geometric growth, the
     grow copy moves the rows up to the bound).  Every launch, allocation and copy is ordered on the engine's stream
     (eng.stream_handle()), whatever stream the caller is on.  capacity: never write a row at or past this index (a
-    step that would is dropped whole and finish() raises CollectOverflow); None: grow as needed."""
+    step that would is dropped whole and finish() raises CollectOverflow); None: grow as needed.
+
+    `memory_group` is any owner of step rows in `_rows`: a MemoryGroup, or an EpisodesBuffer after prepare().  Rows
+    with link columns (_StepRows(links=True), EpisodesBuffer's) take the linked path: end() also writes prev (the
+    row of the same agent's previous step in the same episode, or -1) and tail (the row is its agent's last so far)
+    through a device table of the newest row per (env, id), which the session's first begin() resets.  An agent's
+    chain so ends at its death, at the end of its episode (done or the step cap), or at the end of the session.
+    The linked path refuses rows pushed by other means (they have no links): ValueError at begin()."""
 
     def __init__(self, eng, memory_group, group=0, capacity=None):
         self.eng, self.mg, self.group, self.capacity = eng, memory_group, int(group), capacity
         self._bound = None                  # upper bound of the device row counter; None: no step since finish()
-        self._state = self._scratch = None
+        self._state = self._scratch = self._last = None
         self._src = self._dst = None
+        if memory_group._rows is None:
+            raise ValueError("RolloutCollector: the buffer has no step rows yet (EpisodesBuffer.prepare() makes them)")
         if memory_group._rows.device != "cpu":
             L = lib()
-            for fn in ("mfx_collect_reset", "mfx_collect_begin", "mfx_collect_end"):
+            for fn in ("mfx_collect_reset", "mfx_collect_begin", "mfx_collect_end", "mfx_collect_end_linked",
+                       "mfx_collect_links_reset"):
                 getattr(L, fn).restype = ctypes.c_int
             self._L = L
+
+    @property
+    def linked(self):
+        return bool(getattr(self.mg._rows, "links", False))
 
     # ---- host bookkeeping (runs without a GPU)
     def step_rows(self):
@@ -135,8 +150,11 @@ class RolloutCollector:
         eng, rows = self.eng, self.mg._rows
         E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
         st = ctypes.c_void_p(eng.stream_handle())
+        fresh = self._bound is None
+        if fresh and self.linked and rows.n != 0:
+            raise ValueError("RolloutCollector: %d rows pushed by other means are present; they have no links "
+                             "(clear the buffer first)" % rows.n)
         with torch.cuda.stream(self.eng.torch_stream()):
-            fresh = self._bound is None
             if self._state is None:
                 self._state = torch.zeros(2, dtype=torch.int64, device="cuda")
             if self._scratch is None or self._scratch.numel() < E * rc + 1 + (E + 63) // 64:
@@ -145,6 +163,14 @@ class RolloutCollector:
             if fresh:
                 check(self._L.mfx_collect_reset(ctypes.c_void_p(self._state.data_ptr()), ctypes.c_int64(rows.n), st),
                       "mfx_collect_reset")
+            if self.linked:
+                slots = E * self.id_stride()
+                if self._last is None or self._last.numel() != slots:
+                    self._last = torch.empty(slots, dtype=torch.int64, device="cuda")
+                    fresh = True
+                if fresh:
+                    check(self._L.mfx_collect_links_reset(ctypes.c_void_p(self._last.data_ptr()),
+                                                          ctypes.c_int64(slots), st), "mfx_collect_links_reset")
         V = 1
         for x in rows.obs_shape:
             V *= int(x)
@@ -160,6 +186,8 @@ class RolloutCollector:
         self._dst = _CollectDst(c["obs"].data_ptr(), c["feat"].data_ptr(), c["act"].data_ptr(), c["rew"].data_ptr(),
                                 c["term"].data_ptr(), c["prob"].data_ptr() if rows.use_mean else None,
                                 c["ids"].data_ptr(), cap)
+        self._links = ((ctypes.c_void_p(self._last.data_ptr()), ctypes.c_void_p(c["prev"].data_ptr()),
+                        ctypes.c_void_p(c["tail"].data_ptr())) if self.linked else None)
         self._ptrs = (ctypes.c_void_p(self._scratch.data_ptr()), ctypes.c_void_p(self._scratch.data_ptr() + 4 * E * rc),
                       ctypes.c_void_p(self._state.data_ptr()))
         check(self._L.mfx_collect_begin(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs, st),
@@ -167,9 +195,14 @@ class RolloutCollector:
 
     def end(self):
         assert self._src is not None, "RolloutCollector.end() without begin()"
-        check(self._L.mfx_collect_end(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs,
-                                      ctypes.c_int64(self.id_stride()), ctypes.c_void_p(self.eng.stream_handle())),
-              "mfx_collect_end")
+        if self._links is not None:
+            check(self._L.mfx_collect_end_linked(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs,
+                                                 ctypes.c_int64(self.id_stride()), *self._links,
+                                                 ctypes.c_void_p(self.eng.stream_handle())), "mfx_collect_end_linked")
+        else:
+            check(self._L.mfx_collect_end(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs,
+                                          ctypes.c_int64(self.id_stride()), ctypes.c_void_p(self.eng.stream_handle())),
+                  "mfx_collect_end")
         self._src = None
 
     def discard(self):
@@ -193,6 +226,60 @@ class RolloutCollector:
         self.last_rows = int(n) - self.mg._rows.n      # rows of this session (begin() of its first step .. finish())
         self.mg._rows.n = int(n)
         return int(n)
+
+
+def chain_returns(rew, prev, tails, values, gamma=0.95, numpy1=True):
+    """Discounted returns in place on the float32 column `rew` of step-major rows (HIP kernel k_chain_returns):
+    for chain i, keep = values[i], then along r = tails[i], prev[r], ... to -1: keep = keep * gamma + rew[r];
+    rew[r] = keep, in mf.mfac_returns' two arithmetic forms.  A row index outside its chain's rows raises IndexError
+    (the walk stops before it; the call synchronises the current stream to know)."""
+    assert rew.is_cuda and rew.dtype == torch.float32 and rew.is_contiguous()
+    assert prev.dtype == torch.int64 and prev.is_contiguous() and len(prev) >= len(rew)
+    tails = tails.to(torch.int64).contiguous()
+    values = values.to(torch.float32).contiguous()
+    assert len(values) == len(tails)
+    L = lib()
+    L.mfx_chain_returns.restype = ctypes.c_int
+    if L.mfx_chain_returns(ctypes.c_void_p(rew.data_ptr()), ctypes.c_void_p(prev.data_ptr()),
+                           ctypes.c_void_p(tails.data_ptr()), ctypes.c_void_p(values.data_ptr()),
+                           ctypes.c_int64(len(tails)), ctypes.c_int64(len(rew)), ctypes.c_double(gamma),
+                           int(bool(numpy1)), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
+        L.mfx_last_error.restype = ctypes.c_char_p
+        raise IndexError(L.mfx_last_error().decode())
+    return rew
+
+
+def chain_links(keys):
+    """Host restatement of the linked collector's two columns, for the tests: for the key column of step-major
+    rows, prev[r] = the latest earlier row with the same key (or -1) and tail[r] = no later row has it."""
+    keys = np.asarray(keys, dtype=np.int64)
+    prev = np.full(len(keys), -1, dtype=np.int64)
+    tail = np.zeros(len(keys), dtype=bool)
+    last = {}
+    for r, k in enumerate(keys.tolist()):
+        p = last.get(k, -1)
+        prev[r] = p
+        if p >= 0:
+            tail[p] = False
+        tail[r] = True
+        last[k] = r
+    return prev, tail
+
+
+def chain_returns_host(rew, prev, tails, values, gamma=0.95, numpy1=True):
+    """Host restatement of chain_returns in numpy, for the tests: a new float32 array.  numpy1: keep runs in
+    float64 (the reference's NumPy-1 promotion); else keep and gamma are float32 (NEP 50)."""
+    out = np.array(rew, dtype=np.float32)
+    prev = np.asarray(prev, dtype=np.int64)
+    T = np.float64 if numpy1 else np.float32
+    g = T(gamma)
+    for t, v in zip(np.asarray(tails, dtype=np.int64).tolist(), np.asarray(values, dtype=np.float32)):
+        keep, r = T(v), t
+        while r != -1:
+            keep = T(T(keep * g) + T(out[r]))
+            out[r] = keep
+            r = int(prev[r])
+    return out
 
 
 def check_errors():

@@ -4,6 +4,7 @@
     python -m mfrl_amd.train_battle --algo mfq --envs 256 ...     # batched engine, all in HBM
     python -m mfrl_amd.train_battle --algo mfq --envs 256 --rollout ...   # the device rollout loop (mfq / il)
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --train_backend hip ...   # + the HIP training step
+    python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes ...   # the device rollout loop (ac / mfac)
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -18,7 +19,7 @@ import torch
 import magent
 
 from .algo import spawn_ai, tools
-from .algo.play import play, play_batched, play_rollout
+from .algo.play import play, play_batched, play_rollout, play_rollout_episodes
 
 
 def linear_decay(epoch, x, y):
@@ -52,13 +53,26 @@ def main(argv=None):
     parser.add_argument("--train_backend", type=str, choices=["torch", "hip"], default="torch",
                         help="mfq / il: the minibatch loop on torch autograd (graph replay) or on the hand-written HIP "
                              "training step (mfrl_amd.qtrain)")
+    parser.add_argument("--rollout_episodes", action="store_true",
+                        help="with --envs > 1: the device rollout loop for ac / mfac -- rows collected with their "
+                             "episode chains into the EpisodesBuffer and trained in place")
     args = parser.parse_args(argv)
+    if args.rollout_episodes:
+        if args.rollout:
+            parser.error("--rollout_episodes and --rollout are two loops (ac / mfac and mfq / il): give one")
+        if args.algo not in ("ac", "mfac"):
+            parser.error("--rollout_episodes collects into an EpisodesBuffer: --algo ac or mfac (mfq / il: --rollout)")
+        if args.envs <= 1:
+            parser.error("--rollout_episodes needs the batched engine: --envs > 1")
+        if args.train_backend == "hip":
+            parser.error("--rollout_episodes trains ac / mfac on torch autograd; --train_backend hip trains the Q network")
     if args.train_backend == "hip" and args.algo not in ("mfq", "il"):
         parser.error("--train_backend hip trains the Q network: --algo mfq or il")
     if args.rollout and args.envs <= 1:
         parser.error("--rollout needs the batched engine: --envs > 1")
     if args.rollout and args.algo not in ("mfq", "il"):
-        parser.error("--rollout collects into a MemoryGroup: --algo mfq or il (ac / mfac train from an EpisodesBuffer)")
+        parser.error("--rollout collects into a MemoryGroup: --algo mfq or il (ac / mfac train from an EpisodesBuffer: "
+                     "--rollout_episodes)")
 
     env = magent.GridWorld("battle", map_size=args.map_size)
     env.set_render_dir(os.path.join(args.base_dir, "examples/battle_model", "build/render"))  # train_battle.py:87
@@ -80,7 +94,8 @@ def main(argv=None):
 
         def play_handle(env, n_round, map_size, max_steps, handles, models, print_every, eps=1.0, render=False,
                         train=False):
-            loop = play_rollout if args.rollout else play_batched
+            loop = (play_rollout if args.rollout else play_rollout_episodes if args.rollout_episodes
+                    else play_batched)
             return loop(eng, n_round, map_size, max_steps, models, print_every, eps, train)
     runner = tools.Runner(None, env, handles, args.map_size, args.max_steps, models, play_handle,
                           render_every=args.save_every if args.render else 0, save_every=args.save_every, tau=0.01,
