@@ -5,7 +5,8 @@ Restates, in vectorised numpy of its own:
   * Ising.py:_calc_mask (:7-58)               -> neighbours()
   * IsingWorld.step + Scenario.reward/observation (core.py:99-125, Ising.py:101-119) -> env_step()
   * main_MFQ_Ising.py's episode loop (:84-159) and its numpy RandomState draws -> mfq(),
-    mfq_episodes() (-epi E: episodes in sequence on one stream)
+    mfq_episodes() (-epi E: episodes in sequence on one stream), mfq_given() (the same loop from supplied draws)
+  * k_ising_mfq's Philox draws (csrc/ising_kernels.hip philox / philox_uniform) -> philox(), philox_uniform()
 Pinned bit-exactly against tests/golden/ising_*.npz, which make_ising_fixtures.py recorded by
 running the reference's own Scenario / IsingWorld code.
 """
@@ -13,15 +14,26 @@ import numpy as np
 
 
 def neighbours(n_agents, view=1):
+    """Ascending ids of the cells Ising.py:_calc_mask marks for every agent, [N][K]: the cross of +-1..view along
+    the row and the column, wrapped.  On a side L <= 2 view a wrapped cell coincides with another cell of the
+    cross and the mask holds it once (K < 4 view); every agent must keep the same number of cells."""
     L = int(round(n_agents ** 0.5))
     assert L * L == n_agents
+    if not 1 <= view < L:
+        raise ValueError("the view must be at least 1 and below the lattice side")
     idx = np.arange(n_agents)
     r, c = idx // L, idx % L
     cols = []
     for d in range(1, view + 1):
         for dr, dc in ((-d, 0), (d, 0), (0, -d), (0, d)):
             cols.append(((r + dr) % L) * L + (c + dc) % L)
-    return np.sort(np.stack(cols, 1), axis=1)
+    s = np.sort(np.stack(cols, 1), axis=1)
+    keep = np.ones(s.shape, dtype=bool)
+    keep[:, 1:] = s[:, 1:] != s[:, :-1]
+    K = keep.sum(axis=1)
+    if (K != K[0]).any():
+        raise ValueError("irregular neighbourhood")
+    return s[keep].reshape(n_agents, K[0])
 
 
 def env_step(spins, nbr, actions):
@@ -35,30 +47,56 @@ def env_step(spins, nbr, actions):
     return s, reward, s[nbr], n_up, order
 
 
-def mfq(n_agents, temperature, steps, lr=0.1, act_rate=1.0, decay_rate=0.99, decay_gap=2000, seed=13):
+def mfq(n_agents, temperature, steps, lr=0.1, act_rate=1.0, decay_rate=0.99, decay_gap=2000, seed=13, view=1):
     rs = np.random.RandomState(seed)
     for _ in range(n_agents):                  # make_world -> reset_world
         rs.choice(2)
-    return _episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_gap)
+    return _episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_gap, view)
 
 
 def mfq_episodes(n_agents, temperature, steps, episodes, lr=0.1, act_rate=1.0, decay_rate=0.99, decay_gap=2000,
-                 seed=13):
+                 seed=13, view=1):
     """main_MFQ_Ising.py -epi: every episode on the same RandomState (:84-159)."""
     rs = np.random.RandomState(seed)
     for _ in range(n_agents):
         rs.choice(2)
-    return [_episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_gap) for _ in range(episodes)]
+    return [_episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_gap, view)
+            for _ in range(episodes)]
 
 
-def _episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_gap):
+def _episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_gap, view=1):
     spins = np.array([rs.choice(2) for _ in range(n_agents)], dtype=np.int64)   # env.reset()
-    nbr = neighbours(n_agents)
+    n_upd = int(act_rate * n_agents)
+    return _run(spins, neighbours(n_agents, view), steps, temperature, lr, decay_rate, decay_gap,
+                lambda t: rs.random_sample(n_agents), lambda t: rs.choice(n_agents, n_upd, replace=False))
+
+
+def mfq_given(spins0, u, mask=None, view=1, *, temperature, lr=0.1, decay_rate=0.99, decay_gap=2000):
+    """The episode of mfq() from supplied draws: the spins it starts from, u [T][N] Boltzmann uniforms and, optional,
+    mask [T][ceil(N/32)] uint32 act_group bits (bit i & 31 of word i >> 5 set: agent i updates its Q row at that
+    step; None: every agent, every step).  Stops like the script (order parameter flat for 500 steps)."""
+    spins = np.asarray(spins0).astype(np.int64).reshape(-1)
+    n = len(spins)
+    u = np.asarray(u, dtype=np.float64).reshape(-1, n)
+    ar = np.arange(n)
+    if mask is None:
+        grp = lambda t: ar                                                        # noqa: E731
+    else:
+        mask = np.asarray(mask, dtype=np.uint32).reshape(len(u), -1)
+        grp = lambda t: np.nonzero((mask[t][ar >> 5] >> (ar & 31).astype(np.uint32)) & 1)[0]   # noqa: E731
+    return _run(spins, neighbours(n, view), len(u), temperature, lr, decay_rate, decay_gap, lambda t: u[t], grp)
+
+
+def _run(spins, nbr, steps, temperature, lr, decay_rate, decay_gap, draw_u, draw_grp):
+    """main_MFQ_Ising.py's step loop (:103-159); draw_u(t) then draw_grp(t) are called once per step, in that order.
+    "gaps" is min |u - c0| over the agents at every step run and "min_gap" its minimum: how far the closest draw
+    stood from flipping its action (an exp() a few ulp off moves c0 by ~1e-16)."""
+    n_agents = len(spins)
     K = nbr.shape[1]
     Q = np.zeros((n_agents, K + 1, 2))
     current_t, max_order, done_ = 0.3, 0.0, 0
     orders, nups, acts = [], [], []
-    n_upd = int(act_rate * n_agents)
+    gaps = []
     ar = np.arange(n_agents)
     for t in range(steps):
         if t % decay_gap == 0:
@@ -71,10 +109,11 @@ def _episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_g
         denom = e0 + e1
         p0, p1 = e0 / denom, e1 / denom
         c0 = p0 / (p0 + p1)
-        u = rs.random_sample(n_agents)
+        u = draw_u(t)
+        gaps.append(float(np.abs(u - c0).min()))
         action = (u >= c0).astype(np.int64)
         spins, reward, _obs, n_up, order = env_step(spins, nbr, action)
-        grp = rs.choice(n_agents, n_upd, replace=False)
+        grp = draw_grp(t)
         Q[grp, st[grp], action[grp]] = Q[grp, st[grp], action[grp]] + lr * (reward[grp] - Q[grp, st[grp], action[grp]])
         orders.append(order)
         nups.append(n_up)
@@ -88,7 +127,32 @@ def _episode(rs, n_agents, temperature, steps, lr, act_rate, decay_rate, decay_g
         if done_ == 500:
             break
     return {"q": Q, "order": np.array(orders), "n_up": np.array(nups), "actions": np.stack(acts),
-            "spins": spins, "steps": len(orders)}
+            "spins": spins, "steps": len(orders), "gaps": np.array(gaps), "min_gap": min(gaps)}
+
+
+def philox(c, k0, k1):
+    """Random123 philox4x32-10 as k_ising_mfq's philox() states it: c = four uint32 counter words (arrays broadcast),
+    key (k0, k1) -> the four output words, uint64 arrays holding 32-bit values."""
+    M = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(x, dtype=np.uint64) & M for x in c)
+    k0, k1 = np.uint64(k0) & M, np.uint64(k1) & M
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        n0 = (p1 >> np.uint64(32)) ^ c1 ^ k0
+        n2 = (p0 >> np.uint64(32)) ^ c3 ^ k1
+        c0, c1, c2, c3 = n0, p1 & M, n2, p0 & M
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
+    return c0, c1, c2, c3
+
+
+def philox_uniform(seed, rep, t, i):
+    """k_ising_mfq's Philox draw of replica rep, step t, agent i (arrays broadcast): counter (i, t, rep, 0x5EED1), key
+    (seed, 0xA511E9B3); 53 bits from words 0 and 1 assembled like random_sample ((w0 >> 5) << 26 | w1 >> 6) / 2^53."""
+    i, t, rep = np.broadcast_arrays(np.asarray(i, dtype=np.uint64), np.asarray(t, dtype=np.uint64),
+                                    np.asarray(rep, dtype=np.uint64))
+    w0, w1, _, _ = philox((i, t, rep, np.uint64(0x5EED1)), seed, 0xA511E9B3)
+    bits = ((w0 >> np.uint64(5)) << np.uint64(26)) | (w1 >> np.uint64(6))
+    return bits.astype(np.float64) * (1.0 / 9007199254740992.0)
 
 
 def mfq_loop(n_agents, temperature, steps, lr=0.1, act_rate=1.0, decay_rate=0.99, decay_gap=2000, seed=13):

@@ -31,6 +31,124 @@ def test_oracle_matches_reference_trajectory(name):
     assert out["q"].tobytes() == fx["q_final"].tobytes()          # bit-exact float64 Q table
 
 
+with open(os.path.join(common.GOLDEN, "ising_manifest.json")) as f:
+    _MANIFEST = json.load(f)
+SHAPE_CASES = _MANIFEST["shape_cases"]
+MASK_PAIRS = [tuple(p) for p in _MANIFEST["masks"]["pairs"]]
+
+
+@pytest.mark.parametrize("n,view", MASK_PAIRS)
+def test_neighbour_lists_match_the_reference_masks(n, view):
+    """The product's neighbour_table and the oracle's neighbours against the cells Ising.py:_calc_mask marked
+    (tests/golden/ising_masks.npz), including the sides L <= 2 view where wrapped cells coincide (K < 4 view)."""
+    from mfrl_amd.ising import neighbour_table
+    want = np.load(os.path.join(common.GOLDEN, "ising_masks.npz"))["n%d_v%d" % (n, view)]
+    assert want.shape == (n, _MANIFEST["masks"]["K"]["n%d_v%d" % (n, view)])
+    got = neighbour_table(n, view)
+    assert got.dtype == np.int16
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(ising_oracle.neighbours(n, view), want)
+
+
+def test_mask_fixture_covers_the_collapsed_neighbourhoods():
+    K = _MANIFEST["masks"]["K"]
+    assert [K["n%d_v%d" % p] for p in ((4, 1), (9, 2), (16, 2), (16, 3), (36, 3), (64, 4))] == [2, 4, 6, 6, 10, 14]
+    assert K["n81_v4"] == 16 and K["n49_v3"] == 12 and K["n1089_v2"] == 8
+
+
+def test_oracle_refuses_a_view_that_reaches_round_the_lattice():
+    with pytest.raises(ValueError):
+        ising_oracle.neighbours(9, 3)
+
+
+@pytest.mark.parametrize("name", sorted(SHAPE_CASES))
+def test_oracle_matches_reference_trajectory_off_the_default_line(name):
+    """Views 2 and 3 (K 6 and 12) and a temperature that decays, crosses into its clamp and stops early: actions,
+    order, n_up, the stop step, the final spins and the float64 Q table, bit for bit."""
+    c = SHAPE_CASES[name]
+    fx = np.load(os.path.join(common.GOLDEN, name + ".npz"))
+    out = ising_oracle.mfq(c["n_agents"], c["temperature"], c["steps"], lr=c["lr"], act_rate=c["act_rate"],
+                           decay_rate=c["decay_rate"], decay_gap=c["decay_gap"], seed=c["seed"], view=c["view"])
+    assert out["steps"] == c["stopped_after"] == len(fx["order"])
+    assert out["q"].shape == (c["n_agents"], c["K"] + 1, 2)
+    np.testing.assert_array_equal(out["actions"], fx["actions"])
+    assert out["order"].tobytes() == fx["order"].tobytes()
+    np.testing.assert_array_equal(out["n_up"], fx["n_up"])
+    np.testing.assert_array_equal(out["spins"], fx["spins_final"])
+    assert out["q"].tobytes() == fx["q_final"].tobytes()
+
+
+def test_anneal_fixture_moves_the_temperature():
+    """What makes ising10_anneal worth having: the schedule decays at steps 0, 7, 14, ... and reaches the clamp
+    strictly inside the run, and the run stops early."""
+    c = SHAPE_CASES["ising10_anneal"]
+    cur, seen = 0.3, []
+    for t in range(c["stopped_after"]):
+        if t % c["decay_gap"] == 0:
+            cur *= c["decay_rate"]
+        if cur < c["temperature"]:
+            cur = c["temperature"]
+        seen.append(cur)
+    assert len(set(seen)) > 10 and seen[-1] == c["temperature"] and seen[0] != seen[c["decay_gap"]]
+    assert seen.index(c["temperature"]) > 5 * c["decay_gap"]
+    assert c["stopped_after"] == 547 < c["steps"]
+
+
+@pytest.mark.parametrize("n,view,act_rate,kw", [(100, 1, 1.0, {}), (100, 1, 0.29, {}), (25, 2, 0.5, {"lr": 0.25}),
+                                                (100, 1, 1.0, {"decay_rate": 0.8, "decay_gap": 7})])
+def test_mfq_given_fed_the_reference_draws_equals_mfq(n, view, act_rate, kw):
+    from mfrl_amd.ising import reference_stream
+    T, tau = 80, 0.05 if kw.get("decay_gap") else 0.8
+    spins0, u, mask = reference_stream(13, n, T, act_rate)
+    a = ising_oracle.mfq(n, tau, T, act_rate=act_rate, seed=13, view=view, **kw)
+    b = ising_oracle.mfq_given(spins0, u, mask if act_rate != 1.0 else None, view, temperature=tau, **kw)
+    assert a["steps"] == b["steps"] == T
+    assert a["q"].tobytes() == b["q"].tobytes()
+    assert a["order"].tobytes() == b["order"].tobytes()
+    np.testing.assert_array_equal(a["actions"], b["actions"])
+    np.testing.assert_array_equal(a["n_up"], b["n_up"])
+    np.testing.assert_array_equal(a["spins"], b["spins"])
+    assert a["min_gap"] == b["min_gap"] > 0.0
+    if act_rate != 1.0:
+        assert (np.array([bin(int(w)).count("1") for w in mask.reshape(-1)]).reshape(T, -1).sum(1)
+                == int(act_rate * n)).all()
+
+
+def test_mfq_given_stops_early_on_constant_draws():
+    """u == 0 -> every action 0 (u >= c0 is false for any c0 > 0): order 1.0 from step 0, stop at 500."""
+    out = ising_oracle.mfq_given(np.ones(16, np.uint8), np.zeros((520, 16)), temperature=0.8)
+    assert out["steps"] == 500 and (out["order"] == 1.0).all() and (out["n_up"] == 0).all()
+
+
+def test_philox_known_answers():
+    """Random123's philox4x32-10 known answers (kat_vectors) through the oracle's statement of the kernel's round
+    function, and the 53-bit assembly of philox_uniform from words 0 and 1."""
+    got = ising_oracle.philox((0, 0, 0, 0), 0, 0)
+    assert [int(w) for w in got] == [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]
+    got = ising_oracle.philox((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), 0xa4093822, 0x299f31d0)
+    assert [int(w) for w in got] == [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]
+    got = ising_oracle.philox((0xffffffff,) * 4, 0xffffffff, 0xffffffff)
+    assert [int(w) for w in got] == [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]
+    # vectorised over the counter: every element equals its scalar evaluation
+    i = np.arange(5, dtype=np.uint64)
+    vec = ising_oracle.philox((i, 7, 2, 0x5EED1), 9, 0xA511E9B3)
+    for k in range(5):
+        one = ising_oracle.philox((k, 7, 2, 0x5EED1), 9, 0xA511E9B3)
+        assert [int(w[k]) for w in vec] == [int(w) for w in one]
+    w0, w1 = int(vec[0][3]), int(vec[1][3])
+    u = ising_oracle.philox_uniform(9, 2, 7, i)
+    assert u.dtype == np.float64 and u.shape == (5,)
+    assert float(u[3]) == (((w0 >> 5) << 26) | (w1 >> 6)) / 2.0 ** 53
+    assert ((u >= 0.0) & (u < 1.0)).all()
+    # every argument reaches the counter or the key
+    base = ising_oracle.philox_uniform(9, 2, 7, 3)
+    assert len({float(base), float(ising_oracle.philox_uniform(10, 2, 7, 3)),
+                float(ising_oracle.philox_uniform(9, 3, 7, 3)), float(ising_oracle.philox_uniform(9, 2, 8, 3)),
+                float(ising_oracle.philox_uniform(9, 2, 7, 4))}) == 5
+    t = np.arange(4)[:, None]
+    assert ising_oracle.philox_uniform(9, 1, t, np.arange(6)[None, :]).shape == (4, 6)
+
+
 def test_neighbour_table_matches_oracle():
     from mfrl_amd.ising import neighbour_table
     for n in (16, 100, 400, 900):
