@@ -252,6 +252,19 @@ int mfx_acnet_set_weights(void *handle, const float *d_blob, size_t n_floats, vo
  * (the caller's contract).  input_support_size: the inputs the view layer runs over (0 = dense). */
 int mfx_acnet_set_input_support(void *handle, const uint8_t *mask, int n, void *stream);
 int mfx_acnet_input_support_size(void *handle, int *k);
+/* Acting precision of mfx_acnet_forward / mfx_acnet_act_rollout: 0 = f32 (the default at create), 1 = bf16, the
+ * policy path only (csrc/acnet_bf16_kernels.hip states the contract; same shape range).  In bf16 the operands of every
+ * matrix product -- the view, feature, dense and policy weights, the view and feature inputs, h_view and h_emb after
+ * bias and ReLU, and relu(d) / 0.1 (the f32 division, then one rounding) -- are rounded to nearest even; accumulation
+ * (from the f32 bias), ReLU, softmax, the clip and the draw are f32, the draw's rule and uniforms unchanged; a row's
+ * result depends on neither its place in the batch nor the batch size; an input support does not change the results
+ * (the view layer runs the dense order).  bf16 is acting only: a call with a non-null d_value returns -1 ("bf16 is
+ * acting only" in mfx_last_error()) and launches nothing; d_prob is not read.  Any other value is refused and the
+ * handle keeps its mode.  The f32 blob is kept in both modes: set_precision(1) builds the bf16 images from it on
+ * `stream`, set_weights in bf16 mode rebuilds them, and after set_precision(0) the results are bit-identical to a
+ * handle that never left f32. */
+int mfx_acnet_set_precision(void *handle, int precision, void *stream);
+int mfx_acnet_precision(void *handle, int *precision);
 /* n agents: view [n][view_floats], feature [n][F], prob [n][A] float32 (the MF value head; else null) ->
  * policy [n][A], value [n], act [n] (each may be null); row i drawn with (seed, step, group 0, row i) */
 int mfx_acnet_forward(void *handle, const float *d_view, const float *d_feat, const float *d_prob, int n,

@@ -31,6 +31,7 @@
 
 #include "mfx_common.h"
 #include "policy_gemm.h"
+#include "acnet_bf16.h"
 #include "../../include/magent_amd.h"
 
 namespace mfx {
@@ -71,28 +72,8 @@ struct ACNetDev {
     int vK;
 };
 
-// x / 0.1f, correctly rounded (the reference's dense / 0.1): q = x * 10, one fma residual and one fma correction --
-// equal to the IEEE quotient for every f32 |x| >= 2^-100 (checked exhaustively, scripts/micro/div_tenth.c); tinier
-// nonzero x take the division.
-__device__ __forceinline__ float div_tenth(float x) {
-    const float q = x * 10.0f, r = __builtin_fmaf(-q, 0.1f, x);
-    float y = __builtin_fmaf(r, 10.0f, q);
-    if (__builtin_expect(x != 0.f && __builtin_fabsf(x) < 0x1p-100f, 0)) y = x / 0.1f;
-    return y;
-}
-
-__device__ __forceinline__ uint32_t ac_mix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
-// The uniform of row `row` of group g at step `step` (tests/acnet_ref.py restates it).
-__device__ __forceinline__ float ac_uniform(uint32_t seed, uint32_t step, int g, int row) {
-    const uint32_t k = seed ^ ac_mix32(step * 0x9E3779B9u + (uint32_t)g * 0x632BE5ABu) ^
-                       ac_mix32((uint32_t)row * 0x85EBCA77u + 0x165667B1u);
-    return (float)(ac_mix32(k) >> 8) * (1.0f / 16777216.0f);
-}
-
+// (div_tenth -- x / 0.1f, correctly rounded -- and ac_uniform, the draw's uniform: acnet_bf16.h, shared with the bf16
+// forward)
 // rows (rm.rows): compact agent i -> view / feature row; the action slot as in QRowMap; the prob row of
 // the env (mean field).  d_n: the row count on the device (launch sized for n).  policy_out [n][A],
 // value_out [n], act_out: any may be null.
@@ -399,7 +380,20 @@ struct ACNetHandle {
     uint32_t* vdesc = nullptr;            // [(chunks + 3) * 8]
     float* vrows = nullptr;               // [vK][256]
     float* vimg = nullptr;
+    int precision = 0;                    // 0: f32 (k_acnet), 1: bf16 operands, acting only (acnet_bf16_kernels.hip)
+    ACB16Net b16{};
+    uint4* b16_img = nullptr;             // the bf16 images, allocated by the first switch to bf16
+    bool b16_imaged = false;              // ... and made from the blob's current weights
 };
+
+// The bf16 images of the blob's current weights (allocated on first use).
+int acnet_b16_images(ACNetHandle* q, hipStream_t st) {
+    if (!q->b16_img && hipMalloc(&q->b16_img, acb16_total_units(q->dev.V, q->dev.F) * sizeof(uint4)) != hipSuccess)
+        return fail("acnet: hipMalloc of the bf16 weight images");
+    MFX_HIP(acb16_build(&q->b16, q->dev.w, q->dev.V, q->dev.F, q->dev.A, q->b16_img, st));
+    q->b16_imaged = true;
+    return 0;
+}
 
 __global__ void k_gather_rows(const float* __restrict__ src, const int* __restrict__ idx, int rows, int cols,
                               float* __restrict__ dst) {
@@ -502,6 +496,7 @@ MFX_API int mfx_acnet_destroy(void* handle) {
     if (!q) return 0;
     if (q->blob) (void)hipFree(q->blob);
     if (q->img) (void)hipFree(q->img);
+    if (q->b16_img) (void)hipFree(q->b16_img);
     acnet_support_free(q);
     delete q;
     return 0;
@@ -521,7 +516,26 @@ MFX_API int mfx_acnet_set_weights(void* handle, const float* d_blob, size_t n_fl
                                     const_cast<float*>(q->dev.img[k]), (hipStream_t)stream));
     }
     q->imaged = true;
+    q->b16_imaged = false;
+    if (q->precision == 1) MFX_CHECK(acnet_b16_images(q, (hipStream_t)stream));
     return acnet_support_image(q, (hipStream_t)stream);
+}
+
+// Acting precision: 0 f32 (the default), 1 bf16 matrix operands with f32 accumulation -- the policy path only
+// (acnet_bf16_kernels.hip's contract; a forward that asks for the value is refused).  The f32 blob, its images and
+// the input support stay, so switching needs no re-upload and the f32 results are the same before and after; with
+// weights set, the bf16 images are built on `stream` when the mode lacks them.
+MFX_API int mfx_acnet_set_precision(void* handle, int precision, void* stream) {
+    auto* q = static_cast<ACNetHandle*>(handle);
+    if (precision != 0 && precision != 1) return fail("acnet_set_precision: %d (0: f32, 1: bf16)", precision);
+    if (precision == 1 && q->imaged && !q->b16_imaged) MFX_CHECK(acnet_b16_images(q, (hipStream_t)stream));
+    q->precision = precision;
+    return 0;
+}
+
+MFX_API int mfx_acnet_precision(void* handle, int* precision) {
+    *precision = static_cast<ACNetHandle*>(handle)->precision;
+    return 0;
 }
 
 // The view inputs that can be non-zero: mask[n] (n = view floats; 1 = may be non-zero), e.g. from
@@ -588,6 +602,12 @@ MFX_API int mfx_acnet_input_support_size(void* handle, int* k) {
 static int acnet_run(ACNetHandle* q, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
                      const float* prob, size_t prob_ld, QRowMap rm, int n, const int32_t* d_n,
                      float* policy, float* value, int32_t* act, uint32_t seed, uint32_t step, int group, hipStream_t st) {
+    if (q->precision == 1) {                                        // the policy path only; the support is not used
+        if (value) return fail("acnet: bf16 is acting only (no value head; mfx_acnet_set_precision(0) for the value)");
+        if (!q->b16_imaged) return fail("acnet: the bf16 forward needs weights (mfx_acnet_set_weights)");
+        MFX_HIP(acb16_forward(q->b16, view, view_ld, feat, feat_ld, rm, n, d_n, policy, act, seed, step, group, st));
+        return 0;
+    }
     if (n <= 0) return 0;
     if (q->dev.use_mf && value && !prob) return fail("acnet: the mean-field value head needs prob");
     // persistent workgroups: as many as the CUs hold at once (two per CU with h_emb in LDS), at most one per tile

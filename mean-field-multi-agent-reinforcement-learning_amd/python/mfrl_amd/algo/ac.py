@@ -2,8 +2,8 @@
 
 act samples the clipped softmax policy (tf.multinomial of its log) on the hand-written HIP forward
 (mfrl_amd.policy.ACNetHIP, csrc/acnet_kernels.hip: the policy and a counter-hash draw, its weights re-packed
-only when training changed them); train builds one batch from the
-episode buffer, bootstraps every agent's sequence from the value of its last row, and runs the
+only when training changed them; act_precision = "bf16": its bf16 acting mode, the values still f32); train builds
+one batch from the episode buffer, bootstraps every agent's sequence from the value of its last row, and runs the
 discounted-return recursion keep = keep * gamma + r on the device (HIP kernel mfx_mfac_returns,
 algo/ac.py:305-320), then one Adam step on pg + value_coef * vf + ent_coef * neg_entropy.
 
@@ -27,6 +27,10 @@ from .nets import ACNet
 class ActorCritic:
     _prefix = "ac"
     _use_mf = False
+    # act_dev's / act_rollout's HIP forward: "f32", or "bf16" matrix operands (mfrl_amd.policy.ACNetHIP: the policy and
+    # the draw only).  The bootstrap value of train() / train_rollout() always comes from the f32 forward, so training
+    # is the same, bit for bit, on the same rows whatever this is.
+    act_precision = "f32"
 
     def __init__(self, sess, name, handle, env, value_coef=0.1, ent_coef=0.08, gamma=0.95, batch_size=64,
                  learning_rate=1e-4):
@@ -68,20 +72,23 @@ class ActorCritic:
         view, feat = as_dev(kwargs["state"][0]), as_dev(kwargs["state"][1])
         if self._hip_ok():
             self._draws += 1
-            return self._hip_net().act(view, feat, seed=self.seed, step=self._draws)
+            return self._hip_net(self.act_precision).act(view, feat, seed=self.seed, step=self._draws)
         policy, _ = self.net(view, feat, need_value=False)
         return torch.multinomial(policy, 1).reshape(-1).to(torch.int32)
 
-    def _hip_net(self):
-        """The HIP forward with the network's current weights (re-packed only after they changed)."""
+    def _hip_net(self, precision="f32"):
+        """The HIP forward in mode `precision` with the network's current weights (re-packed only after they
+        changed).  One handle: it keeps the f32 weights in both modes, so acting in bf16 and taking the bootstrap
+        value in f32 is a mode flip, not a second copy."""
         if self._hip is None:
             from ..policy import ACNetHIP
-            self._hip = ACNetHIP(self.view_space, self.feature_space, self.num_actions, self._use_mf)
+            self._hip = ACNetHIP(self.view_space, self.feature_space, self.num_actions, self._use_mf,
+                                 precision=precision)
         key = weights_key(self.net)
         if key != self._hip_key:
             self._hip.load(self.net)
             self._hip_key = key
-        return self._hip
+        return self._hip.set_precision(precision)
 
     def _hip_ok(self):
         return 2 <= self.num_actions <= 32 and int(np.prod(self.view_space)) <= 4096 and self.feature_space[0] <= 256
@@ -140,9 +147,10 @@ class ActorCritic:
         if not self._hip_ok():
             raise ValueError("act_rollout: the HIP forward takes 2..32 actions, views of at most 4096 floats and at "
                              "most 256 features")
-        before = self._hip_key
-        hip = self._hip_net()
-        if self._hip_key != before and eng.stream_handle() != torch.cuda.current_stream().cuda_stream:
+        before = (self._hip_key, self._hip.precision if self._hip is not None else None)
+        hip = self._hip_net(self.act_precision)
+        # (the upload and a mode's first images both run on the current stream)
+        if (self._hip_key, hip.precision) != before and eng.stream_handle() != torch.cuda.current_stream().cuda_stream:
             eng.torch_stream().wait_stream(torch.cuda.current_stream())
         self._draws += 1
         hip.act_rollout(eng, group, seed=self.seed, step=self._draws)

@@ -20,6 +20,16 @@ biases and ReLU stay f32, the Q values are written unrounded.  The Q values then
 the quantisation error (a few 1e-3 of the Q scale, tests/test_policy_bf16_cpu.py), so the greedy action can
 differ where the top two Q values are that close.  The contract is stated in csrc/qnet_bf16_kernels.hip and
 restated in numpy in tests/qnet_bf16_ref.py.
+
+ACNetHIP: the actor-critic network (ActorCritic / MFAC, algo/ac.py) on csrc/acnet_kernels.hip, the same two modes.
+precision="bf16" is the policy path only -- view, feature, dense 512, x / 0.1, policy, the draw -- on
+csrc/acnet_bf16_kernels.hip: the four weight matrices, the view and feature inputs, h_view and h_emb after bias and
+ReLU, and relu(d) / 0.1 (the exact f32 division, then one rounding) go into the products as bf16; accumulation (from
+the f32 bias), ReLU, softmax, the clip and the draw are f32, the draw's rule and uniforms unchanged.  A policy entry
+then moves by about 1e-2 at most (the division by 0.1 amplifies the error; tests/test_acnet_bf16_cpu.py), which a
+sampling policy tolerates and a bootstrap value would not: forward(want_value=True) raises in this mode, and the
+input support, which the f32 kernel uses bit-identically, is not used.  The contract is restated in numpy in
+tests/acnet_bf16_ref.py.
 """
 import ctypes
 
@@ -46,7 +56,7 @@ def _stream():
     return _P(torch.cuda.current_stream().cuda_stream)
 
 
-PRECISIONS = {"f32": 0, "bf16": 1}      # mfx_qnet_set_precision
+PRECISIONS = {"f32": 0, "bf16": 1}      # mfx_qnet_set_precision / mfx_acnet_set_precision
 
 N_BLOCKS = 18      # w1 b1 w2 b2 wd bd we be wp1 bp1 wp2 bp2 w2d b2d wo bo wq bq (policy_kernels.hip)
 
@@ -281,16 +291,21 @@ def pack_acnet(net, view_floats, feature, n_action, use_mf, layout=None):
 
 class ACNetHIP:
     """Forward of ActorCritic / MFAC on the HIP kernel k_acnet: the clipped softmax policy, the value, and the
-    draw of tf.multinomial(log(policy)) from a counter-hash uniform (seed, step, group, row)."""
+    draw of tf.multinomial(log(policy)) from a counter-hash uniform (seed, step, group, row).  precision="bf16":
+    the policy and the draw from bf16 matrix operands (acting only: no value; the module docstring)."""
 
-    def __init__(self, view_space, feature_space, num_actions, use_mf=False):
+    def __init__(self, view_space, feature_space, num_actions, use_mf=False, precision="f32"):
+        if precision not in PRECISIONS:
+            raise ValueError("ACNetHIP: precision %r (one of %s)" % (precision, ", ".join(PRECISIONS)))
+        self.precision = precision
         V = 1
         for d in view_space:
             V *= int(d)
         self.V, self.F, self.A, self.use_mf = V, int(feature_space[0]), int(num_actions), bool(use_mf)
         L = lib()
         for fn in ("mfx_acnet_create", "mfx_acnet_destroy", "mfx_acnet_set_weights", "mfx_acnet_forward",
-                   "mfx_acnet_act_rollout", "mfx_acnet_set_input_support", "mfx_acnet_input_support_size"):
+                   "mfx_acnet_act_rollout", "mfx_acnet_set_input_support", "mfx_acnet_input_support_size",
+                   "mfx_acnet_set_precision", "mfx_acnet_precision"):
             getattr(L, fn).restype = ctypes.c_int
         self._L = L
         self.blob_n, self.offsets = acnet_layout(self.V, self.F, self.A, self.use_mf)
@@ -299,6 +314,8 @@ class ACNetHIP:
         self.handle = hdl
         self._rows = {}
         self._support = None
+        if precision != "f32":
+            check(L.mfx_acnet_set_precision(hdl, PRECISIONS[precision], _P()), "mfx_acnet_set_precision")
 
     def __del__(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
@@ -313,6 +330,17 @@ class ACNetHIP:
         self._blob = self.pack(net).contiguous()
         check(self._L.mfx_acnet_set_weights(self.handle, _ptr(self._blob), ctypes.c_size_t(self.blob_n), _stream()),
               "mfx_acnet_set_weights")
+        return self
+
+    def set_precision(self, precision):
+        """Switch the handle's mode (mfx_acnet_set_precision): the f32 weights stay, the images the mode lacks are
+        built on the current stream, so no re-upload is needed and f32 results are the same before and after."""
+        if precision not in PRECISIONS:
+            raise ValueError("ACNetHIP: precision %r (one of %s)" % (precision, ", ".join(PRECISIONS)))
+        if precision != self.precision:
+            check(self._L.mfx_acnet_set_precision(self.handle, PRECISIONS[precision], _stream()),
+                  "mfx_acnet_set_precision")
+            self.precision = precision
         return self
 
     def set_input_support(self, mask):
@@ -338,7 +366,9 @@ class ACNetHIP:
     def forward(self, view, feature, prob=None, want_policy=True, want_value=False, want_act=True, seed=0, step=0):
         """view [n, ...] (flattened to V), feature [n, F], prob [n, A] (the MF value head) float32 CUDA tensors
         -> (policy [n, A] or None, value [n] or None, actions [n] int32 or None; row i drawn with (seed, step,
-        group 0, row i))."""
+        group 0, row i)).  precision="bf16" is acting only: want_value raises ValueError."""
+        if want_value and self.precision != "f32":
+            raise ValueError("ACNetHIP: precision %r is acting only (no value head)" % self.precision)
         n = view.shape[0]
         view = view.reshape(n, -1).contiguous().float()
         feature = feature.reshape(n, -1).contiguous().float()

@@ -56,6 +56,9 @@ def main(argv=None):
     parser.add_argument("--rollout_episodes", action="store_true",
                         help="with --envs > 1: the device rollout loop for ac / mfac -- rows collected with their "
                              "episode chains into the EpisodesBuffer and trained in place")
+    parser.add_argument("--act_precision", type=str, choices=["f32", "bf16"], default="f32",
+                        help="the acting forward's matrix operands (mfrl_amd.policy: QNetHIP for mfq / il, ACNetHIP "
+                             "for ac / mfac); training and the bootstrap values stay f32")
     args = parser.parse_args(argv)
     if args.rollout_episodes:
         if args.rollout:
@@ -87,6 +90,8 @@ def main(argv=None):
     for m in models:
         if args.train_backend != "torch":
             m.train_backend = args.train_backend
+        if args.act_precision != "f32":
+            m.act_precision = args.act_precision
     play_handle = play
     if args.envs > 1:
         from .battle import BattleBatch

@@ -1,6 +1,7 @@
 """A learned policy on the large-env plans, end to end: a randomly initialised mean-field QNet per group drives a
 BattleBatch through observe / act / step (QNetHIP.act_rollout + BattleBatch.rollout_policy_step, which on these
-plans runs k_rollout_big<ext> + k_observe_items), timed with device events on the engine's stream.
+plans runs k_rollout_big<ext> + k_observe_items), timed with device events on the engine's stream.  --net mfac: two
+MFAC networks (ACNetHIP.act_rollout, the sampled policy, drawn with (--seed, the loop step)) drive the same loop.
 
     python scripts/bench_policy_env.py --map 256 --agents 4096 --envs 2048
     python scripts/bench_policy_env.py --map 40 --envs 1 --steps 2000 --warmup 100
@@ -8,8 +9,9 @@ plans runs k_rollout_big<ext> + k_observe_items), timed with device events on th
 --agents N: two blocks of N / 2 (tests/battle_driver.block_positions, bench.py's placement); 0 (default): the
 reference's generate_map placement (4 % of the cells).  Prints one JSON line: agent-steps/s over the timed window
 (host clock around the window, ending in a synchronise), the forward's and the env step's (step + observation)
-device-event time per loop step, the network's precision (--precision f32 | bf16: QNetHIP's acting mode; with bf16 also
-f32_action_agreement, the share of live agents whose action on the final observation is the f32 network's), and check.ok: after the clock, sampled envs are replayed on the C oracle from
+device-event time per loop step, the network's precision (--precision f32 | bf16: the acting mode of QNetHIP / ACNetHIP;
+with bf16 also f32_action_agreement, the share of live agents whose action on the final observation -- for mfac drawn
+from the same seed and step -- is the f32 network's), and check.ok: after the clock, sampled envs are replayed on the C oracle from
 rollout_init with the actions the device recorded at every step (warm-up included), and the final views, features,
 rewards, mean actions and group sizes must agree bit for bit.
 
@@ -44,6 +46,7 @@ ap.add_argument("--check-envs", type=int, default=4)
 ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--rush-step", action="store_true")
 ap.add_argument("--precision", choices=["f32", "bf16"], default="f32")
+ap.add_argument("--net", choices=["qnet", "mfac"], default="qnet")
 ap.add_argument("--collect", action="store_true")
 ap.add_argument("--collect-gb", type=float, default=48.0)
 a = ap.parse_args()
@@ -104,17 +107,29 @@ if a.rush_step:
     print(json.dumps(res))
     sys.exit(0)
 
-from mfrl_amd.algo.nets import QNet  # noqa: E402
-from mfrl_amd.policy import QNetHIP  # noqa: E402
+from mfrl_amd.algo.nets import ACNet, QNet  # noqa: E402
+from mfrl_amd.policy import ACNetHIP, QNetHIP  # noqa: E402
 
 F, NA = 34, 21
+Net, NetHIP = (ACNet, ACNetHIP) if a.net == "mfac" else (QNet, QNetHIP)
 pols, nets = [], []
 for g in range(2):
     torch.manual_seed(a.seed + g)
-    nets.append(QNet((13, 13, 7), (F,), NA, True).cuda())
-    pols.append(QNetHIP((13, 13, 7), (F,), NA, True, precision=a.precision).load(nets[g]))
+    nets.append(Net((13, 13, 7), (F,), NA, True).cuda())
+    pols.append(NetHIP((13, 13, 7), (F,), NA, True, precision=a.precision).load(nets[g]))
 res["policy_path"] = eng.rollout_policy_path()
+res["net"] = a.net
 res["precision"] = a.precision
+
+
+def act(ps, g, t):
+    """Group g's actions of loop step t from network ps[g] (mfac: the draw of (seed, t))."""
+    if a.net == "mfac":
+        ps[g].act_rollout(eng, g, seed=a.seed, step=t)
+    else:
+        ps[g].act_rollout(eng, g)
+
+
 picks = rck.sample_envs(E, a.check_envs)
 # the sampled envs' actions of every step since rollout_init, copied on the engine's stream after each forward
 log = torch.empty((T, len(picks), 2, rc), dtype=torch.int32, device="cuda")
@@ -132,7 +147,7 @@ def loop_step(t, ev=None):
     if ev:
         ev[0].record()
     for g in range(2):
-        pols[g].act_rollout(eng, g)
+        act(pols, g, t)
     if ev:
         ev[1].record()
     for j, e in enumerate(picks):
@@ -193,9 +208,9 @@ if a.precision != "f32":
     num = torch.empty((E, 2), dtype=torch.int32, device="cuda")
     eng.rollout_copy("group_num", num)
     both = []
-    for ps in (pols, [QNetHIP((13, 13, 7), (F,), NA, True).load(n) for n in nets]):
+    for ps in (pols, [NetHIP((13, 13, 7), (F,), NA, True).load(n) for n in nets]):
         for g in range(2):
-            ps[g].act_rollout(eng, g)
+            act(ps, g, T)
         both.append(torch.empty((E, 2, rc), dtype=torch.int32, device="cuda"))
         eng.rollout_copy("actions", both[-1])
     eng.sync()
