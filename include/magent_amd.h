@@ -404,6 +404,71 @@ int mfx_qtrain_run(void *handle, const mfx_qtrain_ring *ring, long long n, const
                    float *d_stats, void *stream);
 int mfx_qtrain_error(void *handle, int *code, long long *bad_value, void *stream);
 
+/* ---------------------------------------------------------------- AC-network training (csrc/actrain_kernels.hip) */
+/* ActorCritic.train / MFAC.train (algo/ac.py) for the actor-critic network above, f32, on the device: one gradient
+ * over n contiguous rows in place, then one Adam step.  Shapes: those of mfx_acnet_create (view_floats <= 4096,
+ * feature <= 256, 2 <= n_action <= 32, use_mf).
+ * The handle owns three blobs in the layout of mfx_acnet_blob_size -- the parameters and Adam's m and v -- and the
+ * step count.  Padding entries of every blob (K rows past V / F / A, policy columns past A, value columns 1..15) stay
+ * +0 for ever.  The trained parameters can go to mfx_acnet_set_weights device to device.
+ * Rows: mfx_actrain_rows, n >= 1 rows each (row offsets are 64-bit); ret is the reward column after mfx_chain_returns /
+ * mfx_mfac_returns (the bootstrap value and the returns are not this step's).
+ * Forward: the f32 network of acnet_kernels.hip (tests/acnet_ref.py).  Loss, with means over all n rows:
+ *   adv = ret - v (a constant); p = clamp(softmax(z), 1e-10f, 1 - 1e-10f), z = Wp (d / 0.1) + bp; lp = log(p + 1e-6f);
+ *   L = -mean(adv lp[a]) + value_coef mean((ret - v)^2) + ent_coef mean(sum_k p_k lp_k).
+ * Backward: dL/dv = -2 value_coef (ret - v) / n; dL/dp_k = (-adv [k = a] / (p_a + 1e-6) + ent_coef (lp_k + p_k / (p_k +
+ * 1e-6))) / n where the softmax output lies in the clamp's closed interval, else 0 (torch's clamp backward; the bounds
+ * are their f32 values, and float32(1 - 1e-10) = 1, so only the lower bound ever masks); dL/dz_k = s_k (dL/dp_k - sum_j
+ * s_j dL/dp_j); the / 0.1 of the forward is a / 0.1 in the backward; ReLU masks are (kept post-activation value > 0).
+ *   set_hyper        defaults: lr 1e-4, betas 0.9 / 0.999, eps 1e-8 (torch's Adam), value_coef 0.1, ent_coef 0.08; eps
+ *                    must be > 0 (an entry whose g, m and v are all zero divides by it and must stay zero)
+ *   set/get_state    `which` = MFX_ACTRAIN_PARAMS / ADAM_M / ADAM_V; n_floats must be the blob size; a copy on `stream`.
+ *                    Setting the parameters leaves the moments and the step count alone.
+ *   reset_optimizer  zeroes m, v and the step count
+ *   step_count       steps applied (host copy; exact after mfx_actrain_error)
+ *   set_input_support  mask[n] (n = view_floats) or null, the meaning and the caller's contract of
+ *                    mfx_acnet_set_input_support: the view layer's forward and its weight gradient run over the supported
+ *                    inputs only; gradient rows of unsupported inputs are +0; with the unsupported inputs zero the result
+ *                    is bit-identical to the dense one.  Synchronises `stream`.
+ *   set_chunk_rows   rows per chunk, 1 .. 262144 (0: the default, 12288 -- 137 MB of scratch for the kept activations
+ *                    and the backward intermediates at 11 KB per row, plus 24 partial gradient blobs).  Each chunk's
+ *                    weight-gradient partials are added into the gradient blob in chunk order.
+ *   grads            the gradient in blob layout (padding exactly zero) into d_grad_blob and (pg_loss, vf_loss, ent_loss,
+ *                    mean value) -- vf_loss and ent_loss with their coefficients, as ActorCritic.train prints them -- into
+ *                    d_stats (either may be null); no state changes; bit for bit the gradient step applies
+ *   step             grads, then Adam (bias-corrected from the step count), enqueued by this one call; nothing is read
+ *                    back, nothing synchronises
+ *   error            synchronises `stream`; *code = 0 or MFX_ACTRAIN_BAD_ACTION (an action outside [0, n_action)) with
+ *                    the offending value in *bad_value, and clears it.  The action is checked on the device before any
+ *                    load that depends on it; a step with a bad action applies nothing (state and step count unchanged,
+ *                    stats undefined), nor does any later one until this call has cleared the word.
+ * No floating-point atomics, no grid barrier, no spin wait, no cooperative launch: every sum has one fixed order that
+ * depends only on (n, chunk_rows, shape), so equal state, rows and chunk_rows give bitwise equal results.  All launches
+ * go to `stream`; the row columns must stay valid until they have run. */
+typedef struct mfx_actrain_rows {
+    const float *obs;                     /* [n][view_floats] */
+    const float *feat;                    /* [n][feature] */
+    const int32_t *act;                   /* [n] */
+    const float *ret;                     /* [n] */
+    const float *prob;                    /* [n][n_action] (mean field), else null */
+} mfx_actrain_rows;
+enum { MFX_ACTRAIN_PARAMS = 0, MFX_ACTRAIN_ADAM_M = 1, MFX_ACTRAIN_ADAM_V = 2 };
+enum { MFX_ACTRAIN_BAD_ACTION = 1 };
+int mfx_actrain_create(int view_floats, int feature, int n_action, int use_mf, void **handle);
+int mfx_actrain_destroy(void *handle);
+int mfx_actrain_set_hyper(void *handle, double lr, double beta1, double beta2, double eps, double value_coef,
+                          double ent_coef);
+int mfx_actrain_set_state(void *handle, int which, const float *d_blob, size_t n_floats, void *stream);
+int mfx_actrain_get_state(void *handle, int which, float *d_out, size_t n_floats, void *stream);
+int mfx_actrain_reset_optimizer(void *handle, void *stream);
+int mfx_actrain_step_count(void *handle, long long *t);
+int mfx_actrain_set_input_support(void *handle, const uint8_t *mask, int n, void *stream);
+int mfx_actrain_set_chunk_rows(void *handle, int chunk_rows);
+int mfx_actrain_grads(void *handle, const mfx_actrain_rows *rows, long long n, float *d_grad_blob, float *d_stats,
+                      void *stream);
+int mfx_actrain_step(void *handle, const mfx_actrain_rows *rows, long long n, float *d_stats, void *stream);
+int mfx_actrain_error(void *handle, int *code, long long *bad_value, void *stream);
+
 /* ---------------------------------------------------------------- measurement */
 /* The HBM write ceiling on this device, measured in-process beside the bench (csrc/diag_kernels.hip): total_bytes
  * of float4 stores over the device region [d_buf, d_buf + region_bytes), wrapping; shape 0..7: bit 0 = nontemporal

@@ -1,0 +1,175 @@
+"""ACTrainHIP: the hand-written HIP training step (csrc/actrain_kernels.hip) of the reference's actor-critic models.
+
+    ActorCritic.train / MFAC.train   examples/battle_model/algo/ac.py (the loss of :100-127 / :278-303, one Adam step)
+
+The handle owns the parameters and Adam's moments (three blobs in pack_acnet's layout) and the step count.  ``step``
+enqueues one gradient of pg + value_coef * vf + ent_coef * neg_entropy over n contiguous rows, read where they lie,
+and one Adam step, in one call with nothing read back; ``grads`` is the same gradient without the update (the test
+hook, and ActorCritic.train_rollout(step=False)).  f32 throughout; every sum has a fixed order given (n, chunk_rows,
+shape), so equal state and rows give bitwise equal results.  The contract is in include/magent_amd.h (mfx_actrain_*),
+the float64 restatement in tests/actrain_ref.py.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import check, lib
+from .policy import acnet_layout, pack_acnet, unpack_acnet
+
+_P = ctypes.c_void_p
+PARAMS, ADAM_M, ADAM_V = 0, 1, 2
+_ERRORS = {1: "an action outside [0, n_action)"}
+
+
+class _Rows(ctypes.Structure):                # mfx_actrain_rows (include/magent_amd.h)
+    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "feat", "act", "ret", "prob")]
+
+
+class ACTrainError(IndexError):
+    pass
+
+
+def supported(view_space, feature_space, num_actions):
+    """Shapes the kernels take (mfx_acnet_create's): views of at most 4096 floats, feature <= 256, 2..32 actions."""
+    return (1 <= int(np.prod(view_space)) <= 4096 and 1 <= int(feature_space[0]) <= 256 and
+            2 <= int(num_actions) <= 32)
+
+
+def _stream():
+    return _P(torch.cuda.current_stream().cuda_stream)
+
+
+class ACTrainHIP:
+    def __init__(self, view_space, feature_space, num_actions, use_mf=False, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
+                 value_coef=0.1, ent_coef=0.08, chunk_rows=None):
+        if not supported(view_space, feature_space, num_actions):
+            raise ValueError("ACTrainHIP: the HIP training step takes views of at most 4096 floats, feature <= 256 and "
+                             "2..32 actions; got %r, %r, %r" % (tuple(view_space), tuple(feature_space), num_actions))
+        self.V, self.F, self.A = int(np.prod(view_space)), int(feature_space[0]), int(num_actions)
+        self.use_mf = bool(use_mf)
+        L = lib()
+        for fn in ("create", "destroy", "set_hyper", "set_state", "get_state", "reset_optimizer", "step_count",
+                   "set_input_support", "set_chunk_rows", "grads", "step", "error"):
+            getattr(L, "mfx_actrain_" + fn).restype = ctypes.c_int
+        self._L = L
+        self.blob_n, self.offsets = acnet_layout(self.V, self.F, self.A, self.use_mf)
+        hdl = _P()
+        check(L.mfx_actrain_create(self.V, self.F, self.A, int(self.use_mf), ctypes.byref(hdl)), "mfx_actrain_create")
+        self.handle = hdl
+        self._support = None
+        self.set_hyper(lr, betas, eps, value_coef, ent_coef)
+        if chunk_rows:
+            self.set_chunk_rows(chunk_rows)
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self._L.mfx_actrain_destroy(self.handle)
+            self.handle = None
+
+    def set_hyper(self, lr, betas=(0.9, 0.999), eps=1e-8, value_coef=0.1, ent_coef=0.08):
+        D = ctypes.c_double
+        check(self._L.mfx_actrain_set_hyper(self.handle, D(lr), D(betas[0]), D(betas[1]), D(eps), D(value_coef),
+                                            D(ent_coef)), "mfx_actrain_set_hyper")
+
+    def set_chunk_rows(self, chunk_rows):
+        """Rows per chunk of kept activations (0 / None: the default, 12288)."""
+        check(self._L.mfx_actrain_set_chunk_rows(self.handle, int(chunk_rows or 0)), "mfx_actrain_set_chunk_rows")
+
+    # ------------------------------------------------------------------ state
+    def set_state(self, which, blob):
+        """blob: float32 CUDA tensor of blob_n floats in pack_acnet's layout.  Setting PARAMS keeps the moments."""
+        blob = blob.to(device="cuda", dtype=torch.float32).contiguous()
+        check(self._L.mfx_actrain_set_state(self.handle, int(which), _P(blob.data_ptr()), ctypes.c_size_t(blob.numel()),
+                                            _stream()), "mfx_actrain_set_state")
+        blob.record_stream(torch.cuda.current_stream())
+
+    def get_state(self, which):
+        out = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
+        check(self._L.mfx_actrain_get_state(self.handle, int(which), _P(out.data_ptr()), ctypes.c_size_t(self.blob_n),
+                                            _stream()), "mfx_actrain_get_state")
+        return out
+
+    def load(self, net):
+        """Pack the torch ACNet into the handle (the moments and the step count stay)."""
+        self.set_state(PARAMS, pack_acnet(net, self.V, self.F, self.A, self.use_mf, (self.blob_n, self.offsets)))
+
+    def export(self, net):
+        """The handle's parameters copied into the torch module's (policy.unpack_acnet); -> the blob."""
+        blob = self.get_state(PARAMS)
+        unpack_acnet(blob, net, self.V, self.F, self.A, self.use_mf, (self.blob_n, self.offsets))
+        return blob
+
+    def reset_optimizer(self):
+        check(self._L.mfx_actrain_reset_optimizer(self.handle, _stream()), "mfx_actrain_reset_optimizer")
+
+    def step_count(self):
+        t = ctypes.c_longlong()
+        check(self._L.mfx_actrain_step_count(self.handle, ctypes.byref(t)), "mfx_actrain_step_count")
+        return t.value
+
+    def set_input_support(self, mask):
+        """mask: uint8/bool [V], 1 where the view can be non-zero, or None for the dense order (the meaning and the
+        caller's contract of ACNetHIP.set_input_support).  Waits for the current stream."""
+        if mask is None:
+            if self._support is not None:
+                check(self._L.mfx_actrain_set_input_support(self.handle, None, 0, _stream()),
+                      "mfx_actrain_set_input_support")
+            self._support = None
+            return self
+        m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8).reshape(-1))
+        if self._support is None or not np.array_equal(self._support, m):
+            check(self._L.mfx_actrain_set_input_support(self.handle, m.ctypes.data_as(ctypes.c_void_p), int(m.size),
+                                                        _stream()), "mfx_actrain_set_input_support")
+            self._support = m.copy()
+        return self
+
+    # ------------------------------------------------------------------ the step
+    def _rows(self, cols, n):
+        """cols: dict of column tensors (obs [.., V], feat [.., F], act i32, ret f32, prob [.., A] with the mean
+        field), CUDA and contiguous, at least n rows each."""
+        want = {"obs": (torch.float32, self.V), "feat": (torch.float32, self.F), "act": (torch.int32, 1),
+                "ret": (torch.float32, 1)}
+        if self.use_mf:
+            want["prob"] = (torch.float32, self.A)
+        n = int(n)
+        if n < 1:
+            raise ValueError("ACTrainHIP: %d rows (at least 1)" % n)
+        r = _Rows()
+        for k, (dt, width) in want.items():
+            t = cols[k]
+            assert t.is_cuda and t.is_contiguous(), "ACTrainHIP: column %s must be a contiguous CUDA tensor" % k
+            assert t.dtype == dt, "ACTrainHIP: column %s is %s" % (k, t.dtype)
+            assert t.shape[0] >= n and t[0].numel() == width, "ACTrainHIP: column %s has shape %r" % (k, tuple(t.shape))
+            setattr(r, k, t.data_ptr())
+        return r, n
+
+    def grads(self, cols, n):
+        """(gradient blob, stats (pg_loss, vf_loss, ent_loss, mean value)) of rows [0, n).  No state changes."""
+        rows, n = self._rows(cols, n)
+        g = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
+        stats = torch.zeros(4, dtype=torch.float32, device="cuda")
+        check(self._L.mfx_actrain_grads(self.handle, ctypes.byref(rows), ctypes.c_longlong(n), _P(g.data_ptr()),
+                                        _P(stats.data_ptr()), _stream()), "mfx_actrain_grads")
+        return g, stats
+
+    def step(self, cols, n):
+        """One gradient over rows [0, n) and one Adam step; -> the stats on the device.  Nothing synchronises: call
+        check_error() before trusting the result."""
+        rows, n = self._rows(cols, n)
+        stats = torch.zeros(4, dtype=torch.float32, device="cuda")
+        check(self._L.mfx_actrain_step(self.handle, ctypes.byref(rows), ctypes.c_longlong(n), _P(stats.data_ptr()),
+                                       _stream()), "mfx_actrain_step")
+        return stats
+
+    def error(self):
+        """Synchronise; (code, bad value) of the sticky device error, cleared (0: none)."""
+        code, bad = ctypes.c_int(), ctypes.c_longlong()
+        check(self._L.mfx_actrain_error(self.handle, ctypes.byref(code), ctypes.byref(bad), _stream()),
+              "mfx_actrain_error")
+        return code.value, bad.value
+
+    def check_error(self):
+        code, bad = self.error()
+        if code:
+            raise ACTrainError("ACTrainHIP: %s (%d); the step was not applied" % (_ERRORS.get(code, "error %d" % code), bad))

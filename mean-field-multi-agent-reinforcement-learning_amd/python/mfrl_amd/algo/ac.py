@@ -31,6 +31,11 @@ class ActorCritic:
     # the draw only).  The bootstrap value of train() / train_rollout() always comes from the f32 forward, so training
     # is the same, bit for bit, on the same rows whatever this is.
     act_precision = "f32"
+    # train() / train_rollout(): "torch" (autograd per chunk of rows and torch.optim.Adam, the default) or "hip" -- one
+    # step of the hand-written training kernels on the rows in place (mfrl_amd.actrain.ACTrainHIP, f32), after which
+    # the trained blob is copied into self.net and handed to the acting forward device to device.  The two backends
+    # keep separate Adam moments and step counts.
+    _train_backend = "torch"
 
     def __init__(self, sess, name, handle, env, value_coef=0.1, ent_coef=0.08, gamma=0.95, batch_size=64,
                  learning_rate=1e-4):
@@ -51,6 +56,8 @@ class ActorCritic:
         self.optimizer = torch.optim.Adam(self.net.parameters(), lr=self.learning_rate)
         self._hip = None
         self._hip_key = None
+        self._trainer = None        # ACTrainHIP (train_backend "hip"), made at the first training call
+        self._trainer_key = None    # weights_key(self.net) the trainer's parameters were packed from / exported to
         self._draws = 0             # act() calls: the step counter of the device draw
         # the draw's seed: the run's torch seed mixed with the model name, so runs seeded alike draw alike and
         # differently seeded runs differ, as tf.multinomial under TF's seed would; np.random is left
@@ -60,6 +67,53 @@ class ActorCritic:
     @property
     def vars(self):
         return list(self.net.parameters())
+
+    @property
+    def train_backend(self):
+        return self._train_backend
+
+    @train_backend.setter
+    def train_backend(self, name):
+        if name not in ("torch", "hip"):
+            raise ValueError("train_backend %r (torch or hip)" % (name,))
+        if name == "hip" and not self._hip_ok():
+            raise ValueError("train_backend hip: the HIP training step takes 2..32 actions, views of at most 4096 floats "
+                             "and at most 256 features")
+        self._train_backend = name
+
+    def _hip_trainer(self):
+        """The HIP training handle holding the network's current weights (re-packed only when they moved under it:
+        a load(), the Runner's self-play update, a torch-backend step)."""
+        if self._trainer is None:
+            from ..actrain import ACTrainHIP
+            self._trainer = ACTrainHIP(self.view_space, self.feature_space, self.num_actions, self._use_mf,
+                                       lr=self.learning_rate, value_coef=self.value_coef, ent_coef=self.ent_coef)
+        key = weights_key(self.net)
+        if key != self._trainer_key:
+            self._trainer.load(self.net)
+            self._trainer_key = key
+        return self._trainer
+
+    def _hip_train(self, cols, n, step=True, support=None, chunk_rows=None):
+        """One ACTrainHIP step (or, step=False, its gradient as per-parameter tensors) over rows [0, n) of cols where
+        they lie; -> (grads or None, stats tensor).  After a step the trained blob is exported into self.net and set
+        as the acting handle's weights device to device, with both keys moved so that nothing is re-packed."""
+        from ..policy import ACNetHIP, unpack_acnet
+        tr = self._hip_trainer()
+        tr.set_input_support(support)
+        tr.set_chunk_rows(chunk_rows)
+        if not step:
+            g, stats = tr.grads(cols, n)
+            tr.check_error()
+            return unpack_acnet(g, self.net, into=[torch.empty_like(p) for p in self.net.parameters()]), stats
+        stats = tr.step(cols, n)
+        tr.check_error()
+        blob = tr.export(self.net)
+        if self._hip is None:
+            self._hip = ACNetHIP(self.view_space, self.feature_space, self.num_actions, self._use_mf)
+        self._hip.set_blob(blob)
+        self._trainer_key = self._hip_key = weights_key(self.net)
+        return None, stats
 
     def flush_buffer(self, **kwargs):
         self.replay_buffer.push(**kwargs)
@@ -129,6 +183,12 @@ class ActorCritic:
         offsets = torch.zeros(len(counts) + 1, dtype=torch.int64, device="cuda")
         offsets[1:] = torch.cumsum(counts, 0)
         mf.mfac_returns(reward, offsets, keep.float().contiguous(), self.gamma)
+        if self._train_backend == "hip":
+            cols = {"obs": view, "feat": feature, "act": action, "ret": reward, "prob": prob}
+            pg, vf, ent, val = self._hip_train(cols, len(reward))[1].tolist()
+            print("[*] PG_LOSS:", np.round(pg, 6), "/ VF_LOSS:", np.round(vf, 6), "/ ENT_LOSS:", np.round(ent, 6),
+                  "/ VALUE:", val)
+            return
         pg_loss, vf_loss, ent_loss, state_value = self.losses(view, feature, action, reward, prob)
         total = pg_loss + vf_loss + ent_loss
         self.optimizer.zero_grad(set_to_none=True)
@@ -206,6 +266,17 @@ class ActorCritic:
                 _, keep = self.net(c["obs"][tails], c["feat"][tails], p_t)
             replay.chain_returns(c["rew"][:n], c["prev"], tails, keep.float().reshape(-1), self.gamma)
         torch.cuda.current_stream().wait_stream(col.eng.torch_stream())
+        if self._train_backend == "hip":
+            # the rows come from the engine: the view layer runs over its support, as act_rollout's does
+            cols = {"obs": c["obs"], "feat": c["feat"], "act": c["act"], "ret": c["rew"], "prob": prob}
+            grads, stats = self._hip_train(cols, n, step=step, support=col.eng.view_support(col.group),
+                                           chunk_rows=chunk_rows)
+            col.eng.torch_stream().wait_stream(torch.cuda.current_stream())
+            self.replay_buffer.clear()
+            pg, vf, ent, val = stats.tolist()
+            print("[*] PG_LOSS:", np.round(pg, 6), "/ VF_LOSS:", np.round(vf, 6), "/ ENT_LOSS:", np.round(ent, 6),
+                  "/ VALUE:", val, "({} rows, {} chains)".format(n, len(tails)))
+            return grads
         self.optimizer.zero_grad(set_to_none=True)
         sums = torch.zeros(4, dtype=torch.float64, device="cuda")
         for a in range(0, n, chunk):

@@ -289,6 +289,48 @@ def pack_acnet(net, view_floats, feature, n_action, use_mf, layout=None):
     return blob
 
 
+def _acnet_blocks(net, V, F, A, mf):
+    """(block, layer, rows, cols) of every dense layer of a torch ACNet in the blob: the weight block [rows][cols]
+    holds the layer's weight^T in its top-left corner, the next block its bias."""
+    Vp, Fp, Ap = (V + 3) & ~3, (F + 3) & ~3, (A + 3) & ~3
+    out = [(0, net.h_view, Vp, 256), (2, net.h_emb, Fp, 256), (7, net.policy, 512, 32)]
+    if mf:
+        out += [(11, net.emb_prob, Ap, 64), (13, net.dense_prob, 64, 32), (15, net.value_dense, 544, 256),
+                (17, net.value, 256, 16)]
+    else:
+        out += [(9, net.value, 512, 16)]
+    return out
+
+
+@torch.no_grad()
+def unpack_acnet(blob, net, view_floats=None, feature=None, n_action=None, use_mf=None, layout=None, into=None):
+    """The inverse of pack_acnet: the blob's blocks copied in place (copy_) into the parameters of torch ACNet `net`
+    (padding rows / columns dropped).  blob: float32 tensor on any device; the shapes default to the net's own.
+    into: a list of tensors shaped like net.parameters(), in their order, filled instead of the parameters (a gradient
+    blob -> per-parameter gradients); `net` then only gives the shapes."""
+    V = int(net.h_view.in_features if view_floats is None else view_floats)
+    F = int(net.h_emb.in_features if feature is None else feature)
+    A = int(net.policy.out_features if n_action is None else n_action)
+    mf = bool(net.use_mf if use_mf is None else use_mf)
+    n, offsets = layout or acnet_layout(V, F, A, mf)
+    assert blob.numel() == n, "unpack_acnet: %d floats, the layout has %d" % (blob.numel(), n)
+    dst = {id(p): t for p, t in zip(net.parameters(), into)} if into is not None else None
+
+    def out(p):
+        return p if dst is None else dst[id(p)]
+
+    def mat(k, rows, cols):
+        return blob[offsets[k]:offsets[k] + rows * cols].reshape(rows, cols)
+
+    for k, layer, rows, cols in _acnet_blocks(net, V, F, A, mf):
+        out_f, in_f = layer.weight.shape
+        out(layer.weight).copy_(mat(k, rows, cols)[:in_f, :out_f].t())
+        out(layer.bias).copy_(blob[offsets[k + 1]:offsets[k + 1] + out_f])
+    out(net.dense.weight).copy_(torch.cat([mat(4, 512, 256), mat(5, 512, 256)], dim=1).t())
+    out(net.dense.bias).copy_(blob[offsets[6]:offsets[6] + 512])
+    return net if into is None else into
+
+
 class ACNetHIP:
     """Forward of ActorCritic / MFAC on the HIP kernel k_acnet: the clipped softmax policy, the value, and the
     draw of tf.multinomial(log(policy)) from a counter-hash uniform (seed, step, group, row).  precision="bf16":
@@ -328,6 +370,15 @@ class ACNetHIP:
     def load(self, net):
         """Upload the weights of torch ACNet `net` (same shapes)."""
         self._blob = self.pack(net).contiguous()
+        check(self._L.mfx_acnet_set_weights(self.handle, _ptr(self._blob), ctypes.c_size_t(self.blob_n), _stream()),
+              "mfx_acnet_set_weights")
+        return self
+
+    def set_blob(self, blob):
+        """Set the weights from a packed blob on the device (pack_acnet's layout; e.g. ACTrainHIP's parameters):
+        a device-to-device copy, no packing."""
+        assert blob.is_cuda and blob.dtype == torch.float32 and blob.numel() == self.blob_n
+        self._blob = blob.contiguous()
         check(self._L.mfx_acnet_set_weights(self.handle, _ptr(self._blob), ctypes.c_size_t(self.blob_n), _stream()),
               "mfx_acnet_set_weights")
         return self

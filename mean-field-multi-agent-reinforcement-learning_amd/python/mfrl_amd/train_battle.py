@@ -5,6 +5,7 @@
     python -m mfrl_amd.train_battle --algo mfq --envs 256 --rollout ...   # the device rollout loop (mfq / il)
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --train_backend hip ...   # + the HIP training step
     python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes ...   # the device rollout loop (ac / mfac)
+    python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes --ac_train_backend hip ...   # + the HIP step
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -59,7 +60,13 @@ def main(argv=None):
     parser.add_argument("--act_precision", type=str, choices=["f32", "bf16"], default="f32",
                         help="the acting forward's matrix operands (mfrl_amd.policy: QNetHIP for mfq / il, ACNetHIP "
                              "for ac / mfac); training and the bootstrap values stay f32")
+    parser.add_argument("--ac_train_backend", type=str, choices=["torch", "hip"], default="torch",
+                        help="ac / mfac: train() / train_rollout() on torch autograd or on the hand-written HIP "
+                             "training step (mfrl_amd.actrain), with or without --rollout_episodes")
     args = parser.parse_args(argv)
+    if args.ac_train_backend == "hip" and args.algo not in ("ac", "mfac"):
+        parser.error("--ac_train_backend hip trains the actor-critic network: --algo ac or mfac (mfq / il: "
+                     "--train_backend hip)")
     if args.rollout_episodes:
         if args.rollout:
             parser.error("--rollout_episodes and --rollout are two loops (ac / mfac and mfq / il): give one")
@@ -90,6 +97,8 @@ def main(argv=None):
     for m in models:
         if args.train_backend != "torch":
             m.train_backend = args.train_backend
+        if args.ac_train_backend != "torch":
+            m.train_backend = args.ac_train_backend
         if args.act_precision != "f32":
             m.act_precision = args.act_precision
     play_handle = play
