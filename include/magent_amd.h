@@ -190,7 +190,10 @@ int mfx_ising_mfq_run_stream(void *handle, int T, double temperature, double lr,
                              int32_t *steps);
 
 /* ---------------------------------------------------------------- part 4: mean-field kernels */
-/* senario_battle.py:141 */
+/* senario_battle.py:141 -- d_acts [B][rowcap], d_counts [B] -> d_out [B][n_action] float64, 1 <= n_action <= 256.
+ * Row b pools its first n = min(d_counts[b], rowcap) slots (a negative count reads as 0; the row-list kernels cap
+ * the same counts): out[b][a] = (slots equal to a) / n.  An action outside [0, n_action) is counted in no entry
+ * while n stays the divisor; n = 0 gives a row of NaN. */
 int mfx_mean_action(const int32_t *d_acts, const int32_t *d_counts, int B, int rowcap, int n_action, double *d_out,
                     void *stream);
 /* algo/base.py:192-220 */
@@ -291,6 +294,12 @@ int mfx_rows_copy_shift(int n_cols, void *const *dst, const void *const *src, co
                         const int64_t *d_idx, int64_t src_mod, int64_t src_rows, int64_t dst_start, int64_t dst_cap,
                         int64_t n, uint32_t shift_mask, int64_t shift, void *stream);
 int mfx_rows_copy_error(int64_t *bad_index, void *stream);
+/* The launch form mfx_rows_copy_shift would take for these columns (pointers, row sizes and MFX_ROWS_PIPE decide it;
+ * nothing is launched): out[0] = 0 the one-row-per-wave form k_rows_copy / 1 the pipelined k_rows_pipe<NW, NU>,
+ * out[1] = NW, out[2] = NU (both 0 for k_rows_copy), out[3] = the narrow units of a row, out[4 + k] = column k's
+ * class: 0 narrow moved in dwords, 1 narrow moved in bytes, 2 wide (>= 512 B).  out: 4 + n_cols ints. */
+int mfx_rows_copy_plan(int n_cols, void *const *dst, const void *const *src, const int64_t *row_bytes,
+                       uint32_t shift_mask, int32_t *out);
 
 /* Replay rows straight from the device rollout loop (csrc/collect_kernels.hip): one row of the step-row columns per
  * live agent of one group for every mfx_battle_rollout_policy_step, with no host work per step.

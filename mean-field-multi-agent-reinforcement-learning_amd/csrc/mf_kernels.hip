@@ -14,11 +14,12 @@
 namespace mfx {
 
 // One workgroup per group row: histogram in LDS, then count / n in float64 (np.mean of one-hot
-// rows sums exact 0/1 values, so the result is exactly count / n).
+// rows sums exact 0/1 values, so the result is exactly count / n).  n = counts[b] capped at the rowcap slots the
+// row holds (the row-list kernels cap the same counts), a negative count read as 0.
 __global__ void __launch_bounds__(256) k_mean_action(const int32_t* __restrict__ acts, const int32_t* __restrict__ counts,
                                                      int rowcap, int n_action, double* __restrict__ out) {
     __shared__ int hist[256];
-    const int b = blockIdx.x, n = counts[b];
+    const int b = blockIdx.x, n = max(0, min(counts[b], rowcap));
     for (int k = threadIdx.x; k < n_action; k += blockDim.x) hist[k] = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += blockDim.x) {

@@ -300,29 +300,26 @@ __global__ void __launch_bounds__(256) k_rows_pipe(RowCols c, PipeWide wd, const
 
 using namespace mfx;
 
-extern "C" {
+// The launch form of one move, decided on the host from the columns alone (mfx_rows_copy_plan reports it): which
+// columns are narrow (dword or byte units) and which wide, and whether the pipelined form takes the call.
+struct RowsPlan {
+    RowCols c;
+    PipeWide wd;
+    int n_wide;
+    bool pipe;                 // k_rows_pipe<nw, nu>; else k_rows_copy
+    int nw, nu;
+};
 
-// For i in [0, n): row s = idx ? idx[i] : i (taken modulo src_mod when src_mod > 0) of every source column
-// to row d = dst_start + i (modulo dst_cap when dst_cap > 0) of the destination column.  n_cols <= 12;
-// row_bytes[k]: bytes per row of column k.  Destination rows of one call must be distinct (a ring shorter
-// than n would make two rows race for a slot: the caller skips the rows a ring would overwrite).
-// src_rows: rows every source column holds; without src_mod an index in [-src_rows, 0) counts from the end (numpy's
-// indexing); any other index outside [0, src_rows) skips its row and is reported by mfx_rows_copy_error.
-// Columns k with bit k of shift_mask set read row idx[i] + shift instead (before the modulo; their row is checked
-// the same way): MemoryGroup.sample's next-state columns, (idx + 1) % nb_entries, in the same launch.
-MFX_API int mfx_rows_copy_shift(int n_cols, void* const* dst, const void* const* src, const int64_t* row_bytes,
-                                const int64_t* d_idx, int64_t src_mod, int64_t src_rows, int64_t dst_start,
-                                int64_t dst_cap, int64_t n, uint32_t shift_mask, int64_t shift, void* stream) {
+static int rows_cols_ok(int n_cols, uint32_t shift_mask) {
     if (n_cols < 1 || n_cols > kRowCols) return fail("rows_copy: 1..%d columns, got %d", kRowCols, n_cols);
     if (shift_mask >> n_cols) return fail("rows_copy: shift mask 0x%x names columns past %d", shift_mask, n_cols);
-    if (src_mod > src_rows) return fail("rows_copy: modulo %lld over %lld source rows", (long long)src_mod,
-                                        (long long)src_rows);
-    if (!d_idx && n > src_rows) return fail("rows_copy: %lld rows from %lld source rows", (long long)n,
-                                            (long long)src_rows);
-    if (n < 0 || (dst_cap > 0 && n > dst_cap)) return fail("rows_copy: %lld rows into a ring of %lld", (long long)n,
-                                                           (long long)dst_cap);
-    if (n == 0) return 0;
-    RowCols c{};
+    return 0;
+}
+
+static int rows_plan(int n_cols, void* const* dst, const void* const* src, const int64_t* row_bytes,
+                     uint32_t shift_mask, int64_t shift, RowsPlan& p) {
+    p = RowsPlan{};
+    RowCols& c = p.c;
     c.n = n_cols;
     c.shift = shift_mask;
     c.shift_by = shift_mask ? shift : 0;
@@ -344,7 +341,7 @@ MFX_API int mfx_rows_copy_shift(int n_cols, void* const* dst, const void* const*
     for (int k = n_cols; k <= kRowCols; ++k) c.ustart[k] = units;
     // the pipelined form takes at most two wide columns (4-B aligned, <= 64 x 4 kPipeQ + 3 dwords) and <= 64 kPipeU
     // units
-    PipeWide wd{};
+    PipeWide& wd = p.wd;
     int n_wide = 0;
     bool wide_ok = true;
     for (int k = 0; k < n_cols; ++k) {
@@ -360,11 +357,43 @@ MFX_API int mfx_rows_copy_shift(int n_cols, void* const* dst, const void* const*
         }
         ++n_wide;
     }
-    const bool pipe = n_wide <= kPipeW && wide_ok && units <= 64 * kPipeU;
+    p.n_wide = n_wide;
     const char* pe = getenv("MFX_ROWS_PIPE");              // 0: the one-row-per-wave form (tests)
     const int use_pipe = pe ? atoi(pe) : 1;
+    p.pipe = n_wide <= kPipeW && wide_ok && units <= 64 * kPipeU && use_pipe;
+    p.nw = p.pipe ? (n_wide == 2 ? 2 : 1) : 0;
+    p.nu = p.pipe ? (units > 64 ? 2 : 1) : 0;
+    return 0;
+}
+
+extern "C" {
+
+// For i in [0, n): row s = idx ? idx[i] : i (taken modulo src_mod when src_mod > 0) of every source column
+// to row d = dst_start + i (modulo dst_cap when dst_cap > 0) of the destination column.  n_cols <= 12;
+// row_bytes[k]: bytes per row of column k.  Destination rows of one call must be distinct (a ring shorter
+// than n would make two rows race for a slot: the caller skips the rows a ring would overwrite).
+// src_rows: rows every source column holds; without src_mod an index in [-src_rows, 0) counts from the end (numpy's
+// indexing); any other index outside [0, src_rows) skips its row and is reported by mfx_rows_copy_error.
+// Columns k with bit k of shift_mask set read row idx[i] + shift instead (before the modulo; their row is checked
+// the same way): MemoryGroup.sample's next-state columns, (idx + 1) % nb_entries, in the same launch.
+MFX_API int mfx_rows_copy_shift(int n_cols, void* const* dst, const void* const* src, const int64_t* row_bytes,
+                                const int64_t* d_idx, int64_t src_mod, int64_t src_rows, int64_t dst_start,
+                                int64_t dst_cap, int64_t n, uint32_t shift_mask, int64_t shift, void* stream) {
+    MFX_CHECK(rows_cols_ok(n_cols, shift_mask));
+    if (src_mod > src_rows) return fail("rows_copy: modulo %lld over %lld source rows", (long long)src_mod,
+                                        (long long)src_rows);
+    if (!d_idx && n > src_rows) return fail("rows_copy: %lld rows from %lld source rows", (long long)n,
+                                            (long long)src_rows);
+    if (n < 0 || (dst_cap > 0 && n > dst_cap)) return fail("rows_copy: %lld rows into a ring of %lld", (long long)n,
+                                                           (long long)dst_cap);
+    if (n == 0) return 0;
+    RowsPlan p;
+    MFX_CHECK(rows_plan(n_cols, dst, src, row_bytes, shift_mask, shift, p));
+    const RowCols& c = p.c;
+    const PipeWide& wd = p.wd;
+    const int n_wide = p.n_wide;
     const int64_t wgs = (n + 3) / 4;
-    if (pipe && use_pipe) {
+    if (p.pipe) {
         // persistent-sized grid, each wave walking its rows two in flight
         static const int cus = [] {
             int dev = 0, n_cu = 0;
@@ -380,8 +409,8 @@ MFX_API int mfx_rows_copy_shift(int n_cols, void* const* dst, const void* const*
         const int per_cu = n_wide == 2 ? 2 : 3;
         const int64_t cap = (int64_t)cus * per_cu;
         const int grid = (int)(wgs < cap ? wgs : cap);
-        auto* kern = n_wide == 2 ? (units > 64 ? k_rows_pipe<2, 2> : k_rows_pipe<2, 1>)
-                                 : (units > 64 ? k_rows_pipe<1, 2> : k_rows_pipe<1, 1>);
+        auto* kern = p.nw == 2 ? (p.nu == 2 ? k_rows_pipe<2, 2> : k_rows_pipe<2, 1>)
+                               : (p.nu == 2 ? k_rows_pipe<1, 2> : k_rows_pipe<1, 1>);
         kern<<<grid, 256, 0, (hipStream_t)stream>>>(c, wd, d_idx, src_mod, src_rows, dst_start, dst_cap, n);
         MFX_HIP(hipGetLastError());
         return 0;
@@ -389,6 +418,23 @@ MFX_API int mfx_rows_copy_shift(int n_cols, void* const* dst, const void* const*
     const int grid = (int)(wgs < 65536 ? wgs : 65536);
     k_rows_copy<<<grid, 256, 0, (hipStream_t)stream>>>(c, d_idx, src_mod, src_rows, dst_start, dst_cap, n);
     MFX_HIP(hipGetLastError());
+    return 0;
+}
+
+// The launch form mfx_rows_copy_shift would choose for these columns, without launching anything (MFX_ROWS_PIPE is
+// honoured as there): out[0] = 0 k_rows_copy / 1 k_rows_pipe<NW, NU>, out[1] = NW, out[2] = NU (both 0 for
+// k_rows_copy), out[3] = the narrow units, out[4 + k] = column k's class: 0 narrow in dwords, 1 narrow in bytes, 2 wide.
+MFX_API int mfx_rows_copy_plan(int n_cols, void* const* dst, const void* const* src, const int64_t* row_bytes,
+                               uint32_t shift_mask, int32_t* out) {
+    if (!out) return fail("rows_copy_plan: null argument");
+    MFX_CHECK(rows_cols_ok(n_cols, shift_mask));
+    RowsPlan p;
+    MFX_CHECK(rows_plan(n_cols, dst, src, row_bytes, shift_mask, 0, p));
+    out[0] = p.pipe ? 1 : 0;
+    out[1] = p.nw;
+    out[2] = p.nu;
+    out[3] = p.c.ustart[kRowCols];
+    for (int k = 0; k < n_cols; ++k) out[4 + k] = p.c.ubytes[k] == 4 ? 0 : p.c.ubytes[k] == 1 ? 1 : 2;
     return 0;
 }
 

@@ -20,9 +20,22 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _dtype(what, **tensors):
+    """Refuse a tensor of another dtype before any library call: the kernels read raw bytes."""
+    for name, (t, want) in tensors.items():
+        if t.dtype != want:
+            raise TypeError("%s: %s must be %s, got %s" % (what, name, want, t.dtype))
+
+
 def mean_action(actions, counts, n_action):
-    """actions int32 [B, rowcap] (rows past counts[b] ignored), counts int32 [B] -> float64 [B, n_action]."""
+    """actions int32 [B, rowcap], counts int32 [B] -> float64 [B, n_action]: row b is the mean of the one-hot rows
+    of its first n = min(counts[b], rowcap) slots (a count above rowcap is capped, as the row-list kernels cap it; a
+    negative one reads as 0).  An action outside [0, n_action) is counted in no entry while n stays the divisor; n = 0
+    gives a row of NaN.  Any other dtype raises TypeError."""
+    _dtype("mean_action", actions=(actions, torch.int32), counts=(counts, torch.int32))
     B, rowcap = actions.shape
+    if counts.shape != (B,):
+        raise ValueError("mean_action: counts of shape %s for %d rows" % (tuple(counts.shape), B))
     out = torch.empty((B, n_action), dtype=torch.float64, device=actions.device)
     L = lib()
     L.mfx_mean_action.restype = ctypes.c_int
@@ -32,8 +45,13 @@ def mean_action(actions, counts, n_action):
 
 
 def mfq_target(e_q, t_q, rewards, dones, gamma=0.95):
-    """target = r + (1 - done) * t_q[argmax e_q] * gamma, float64 [M] (dones: bool/uint8 [M])."""
+    """target = r + (1 - done) * t_q[argmax e_q] * gamma, float64 [M]; e_q, t_q float32 [M, A], rewards float32 [M]
+    (any other dtype raises TypeError); dones: bool/uint8 [M], any non-zero byte is done."""
+    _dtype("mfq_target", e_q=(e_q, torch.float32), t_q=(t_q, torch.float32), rewards=(rewards, torch.float32))
     M, A = e_q.shape
+    if t_q.shape != (M, A) or rewards.shape != (M,) or dones.shape != (M,):
+        raise ValueError("mfq_target: e_q %s, t_q %s, rewards %s, dones %s" % tuple(
+            tuple(x.shape) for x in (e_q, t_q, rewards, dones)))
     out = torch.empty(M, dtype=torch.float64, device=e_q.device)
     d = dones.to(torch.uint8).contiguous()
     L = lib()
@@ -44,9 +62,16 @@ def mfq_target(e_q, t_q, rewards, dones, gamma=0.95):
 
 
 def mfac_returns(rewards, offsets, values, gamma=0.95, numpy1=True):
-    """Per-episode discounted returns, in place on float32 rewards; offsets int64 [E+1].
+    """Per-episode discounted returns, in place on float32 contiguous rewards; offsets int64 [E+1], values float32
+    [E] (any other dtype raises TypeError, a non-contiguous rewards or another length ValueError).
 
     numpy1: the promotion of the reference's NumPy-1 era (keep in float64); False: NEP 50 (float32)."""
+    _dtype("mfac_returns", rewards=(rewards, torch.float32), offsets=(offsets, torch.int64),
+           values=(values, torch.float32))
+    if not rewards.is_contiguous():
+        raise ValueError("mfac_returns: rewards must be contiguous (the returns are written in place)")
+    if offsets.dim() != 1 or values.dim() != 1 or len(offsets) != len(values) + 1:
+        raise ValueError("mfac_returns: %d offsets for %d values (one more is needed)" % (len(offsets), len(values)))
     L = lib()
     L.mfx_mfac_returns.restype = ctypes.c_int
     check(L.mfx_mfac_returns(_p(rewards), _p(offsets.contiguous()), _p(values.contiguous()), len(values),

@@ -48,6 +48,23 @@ def rows_copy(dst, src, idx=None, src_mod=0, dst_start=0, dst_cap=0, n=None, shi
           "mfx_rows_copy_shift")
 
 
+def rows_plan(dst, src, shift_mask=0):
+    """The launch form rows_copy would take for these columns (mfx_rows_copy_plan; nothing is launched): a dict of
+    form (0 = k_rows_copy, 1 = k_rows_pipe), nw and nu (the pipelined form's template arguments, 0 otherwise), units
+    (narrow units of a row) and cols (per column: 0 narrow in dwords, 1 narrow in bytes, 2 wide).  MFX_ROWS_PIPE is
+    honoured as by the launcher.  For the tests: a case asserts the form it was written for."""
+    assert len(dst) == len(src) and 0 < len(dst) <= _MAX_COLS
+    rb = [d.element_size() * (d[0].numel() if d.dim() > 1 else 1) for d in dst]
+    k = len(dst)
+    L = lib()
+    L.mfx_rows_copy_plan.restype = ctypes.c_int
+    P = ctypes.c_void_p * k
+    out = (ctypes.c_int32 * (4 + k))()
+    check(L.mfx_rows_copy_plan(k, P(*[d.data_ptr() for d in dst]), P(*[s.data_ptr() for s in src]),
+                               (ctypes.c_int64 * k)(*rb), ctypes.c_uint32(int(shift_mask)), out), "mfx_rows_copy_plan")
+    return {"form": out[0], "nw": out[1], "nu": out[2], "units": out[3], "cols": list(out[4:4 + k])}
+
+
 def rollout_key(env, episode, agent_id, n_envs, id_stride):
     """The agent key of a collected row (csrc/collect_kernels.hip collect_key): injective over env < n_envs,
     episode >= 0 and agent_id < id_stride.  Ids restart at 0 in every episode, so the episode number is part of it."""

@@ -7,6 +7,7 @@ whose uniform lies more than 2 e_c from every boundary of the exact cumulative p
 <= e_p and |p - exact| <= 2 e_p.  Both come from the CPU, not from the kernel: re-running the reference with f32
 accumulation in three other orders moved the policy by at most 0.17 e_p, while a layout or permutation mistake moves
 it by the policy scale, 10 - 40 times e_p."""
+import copy
 import ctypes
 import os
 import re
@@ -142,7 +143,7 @@ def test_off_the_battle_shape(case):
     for name, (v, f) in (("view", (0 * r.view, r.feat)), ("feat", (r.view, 0 * r.feat))):     # the precondition
         moved = float(np.median(np.abs(ref.forward(r.blob, r.layout[1], V, F, A, mf, v, f) - quant).max(1)))
         assert moved > 2.0 * e_p, (name, moved, e_p)
-    hip = _hip(r.net.cuda(), mf, shape=((V,), (F,), A))
+    hip = _hip(copy.deepcopy(r.net).cuda(), mf, shape=((V,), (F,), A))      # (r is cached: its CPU net stays put)
     pol, _, act = hip.forward(torch.from_numpy(r.view).cuda(), torch.from_numpy(r.feat).cuda(), seed=SEED, step=STEP)
     torch.cuda.synchronize()
     pol, act = pol.cpu().numpy(), act.cpu().numpy()

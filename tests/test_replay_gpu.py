@@ -1,6 +1,8 @@
 """The replay rows' HIP mover (mfx_rows_copy, csrc/replay_kernels.hip) against torch indexing: gathers with and
-without an index list, modulo a source length, into a ring with wrap; column widths that take the 16-B,
-4-B and byte paths (view rows of 4,732 B, int32, bool, float64 x 21).  The buffers' semantics against the
+without an index list, modulo a source length, into a ring with wrap; the Battle row's columns: a wide view row of
+4,732 B (the dword path of k_rows_copy, 16-B units and a 3-dword tail in k_rows_pipe) and narrow columns below 512 B
+moved unit by unit, in dwords (int32, float32 x 4, float64 x 21) or bytes (bool).  k_rows_copy's 16-B path, the other
+widths, tails and limits: tests/test_rows_shapes_gpu.py.  The buffers' semantics against the
 reference's own MemoryGroup / EpisodesBuffer: test_algo_gpu.py::test_device_replay_matches_reference_fixture."""
 import pytest
 import torch
@@ -9,10 +11,10 @@ pytestmark = pytest.mark.gpu
 
 
 def _cols(n, gen):
-    return [torch.rand((n, 13, 13, 7), generator=gen, device="cuda"),            # 4,732 B: 4-B path
+    return [torch.rand((n, 13, 13, 7), generator=gen, device="cuda"),            # 4,732 B: wide, 4-B path
             torch.randint(0, 21, (n,), generator=gen, device="cuda", dtype=torch.int32),
             torch.rand((n,), generator=gen, device="cuda") < 0.5,                 # 1 B: byte path
-            torch.rand((n, 4), generator=gen, device="cuda"),                     # 16 B: 16-B path
+            torch.rand((n, 4), generator=gen, device="cuda"),                     # 16 B: narrow, 4 dword units
             torch.rand((n, 21), generator=gen, device="cuda", dtype=torch.float64)]
 
 
