@@ -363,6 +363,64 @@ int mfx_collect_links_reset(int64_t *d_last, int64_t n, void *stream);
 int mfx_chain_returns(float *d_rew, const int64_t *d_prev, const int64_t *d_tails, const float *d_value,
                       int64_t n_tails, int64_t n_rows, double gamma, int numpy1, void *stream);
 
+/* ---------------------------------------------------------------- part 7: episode outcomes (csrc/score_kernels.hip) */
+/* The scorekeeper of the device rollout loop: per-episode outcomes of every env with Runner.run's own win rule
+ * (algo/tools.py, train=False), with no host work per step.  Group 0 is "main", group 1 "opponent"; two groups only
+ * (any other n_groups is refused on the host).  The sources are the rollout buffers of mfx_battle_rollout_buffer, or
+ * any device arrays of the same layout.
+ *   mfx_score_attach   after the policy observe, before the first policy step: per env, carry = {n_cur[g] = start[g] =
+ *                      group_num[e][g], ep = (int64)stats[e][0], steps0 = agent_steps[e], len = 0}, ret0[g] =
+ *                      stats[e][1 + g]; zeroes totals, log and state.
+ *   mfx_score_update   exactly once after every mfx_battle_rollout_policy_step, one launch.  Per env:
+ *                      guard   agent_steps[e] - steps0 must be n_cur[0] + n_cur[1], else error bit 0 (a step was not
+ *                              scored, or was scored twice); (int64)stats[e][0] - ep must be 0 or 1, else bit 1; a
+ *                              carried or new group size outside [0, rowcap] is bit 2.  An env that fails one is not
+ *                              scored in this call -- totals and log untouched -- and its carry is taken afresh as
+ *                              attach does (n_cur, start, ep, steps0, len and ret0, not only n_cur and steps0), so
+ *                              later calls stay in bounds and in step.  What that costs: an episode that ends in
+ *                              the same call as a failed guard appears in neither the totals nor the log, and the
+ *                              episode the env is in counts its length and start sizes from this call on.  The
+ *                              sticky word tells the host that the totals are incomplete (finish() raises).
+ *                      surv[g] = non-zero bytes among alive[e][g][0 .. n_cur[g]); later bytes are never counted.
+ *                      len += 1; the episode ended iff (int64)stats[e][0] == ep + 1.  Then, with nums[g] = n_cur[g]
+ *                      (the members of the last step, those that died in it included: get_num before clear_dead),
+ *                      kill[0] = start[0] - nums[1], kill[1] = start[1] - nums[0]; winner = 0 (kill[0] > kill[1]),
+ *                      1 (<) or 2 (equal: counts for both); ret[g] = stats[e][1 + g] - ret0[g].  The record goes to
+ *                      log[e][episodes scored so far] when that index is < ep_cap, else dropped += 1.  totals +=
+ *                      episode, win / tie, kills, len.  Then len = 0, ep += 1, ret0 = stats now.
+ *                      carry   n_cur[g] = group_num[e][g], steps0 = agent_steps[e]; at an episode end start = n_cur.
+ *                      When an env's episode count reaches `target` (>= 1), state[0] += 1 (integer atomic).
+ * Everything but the two state words is written by its env's own wave; no float atomics; nothing depends on the launch
+ * order.  Nothing synchronises and nothing is read back: the host reads totals, log and state when it wants them. */
+typedef struct mfx_score_src {
+    const int32_t *group_num;             /* [E][2] */
+    const uint8_t *alive;                 /* [E][2][rowcap] */
+    const double *stats;                  /* [E][4] */
+    const int64_t *agent_steps;           /* [E] */
+    int32_t n_envs, n_groups, rowcap;     /* rowcap: a multiple of 4 */
+} mfx_score_src;
+typedef struct mfx_score_record {         /* 48 bytes */
+    int32_t len, nums[2], surv[2], kill[2], winner;
+    double ret[2];
+} mfx_score_record;
+enum { MFX_SCORE_N_CUR = 0, MFX_SCORE_START = 2, MFX_SCORE_EP = 4, MFX_SCORE_STEPS0 = 5, MFX_SCORE_LEN = 6,
+       MFX_SCORE_CARRY = 8 };             /* int64 words of an env's carry ([7] is zero) */
+enum { MFX_SCORE_EPISODES = 0, MFX_SCORE_MAIN_WINS = 1, MFX_SCORE_OPPO_WINS = 2, MFX_SCORE_TIES = 3,
+       MFX_SCORE_KILLS = 4, MFX_SCORE_STEPS = 6, MFX_SCORE_DROPPED = 7, MFX_SCORE_TOTALS = 8 };
+enum { MFX_SCORE_ERR_STEP = 1, MFX_SCORE_ERR_EPISODE = 2, MFX_SCORE_ERR_COUNT = 4 };
+typedef struct mfx_score_dst {
+    int64_t *carry;                       /* [E][MFX_SCORE_CARRY] */
+    double *ret0;                         /* [E][2] */
+    int64_t *totals;                      /* [E][MFX_SCORE_TOTALS] */
+    mfx_score_record *log;                /* [E][ep_cap] */
+    int64_t *state;                       /* [2]: envs that reached target, the sticky error word */
+    int64_t ep_cap, target;               /* ep_cap >= 0 (0: log may be null), target >= 1 */
+} mfx_score_dst;
+/* bytes of carry, ret0, totals, log, state for n_envs envs and ep_cap records (host) */
+int mfx_score_sizes(int n_envs, int64_t ep_cap, size_t bytes[5]);
+int mfx_score_attach(const mfx_score_src *src, const mfx_score_dst *dst, void *stream);
+int mfx_score_update(const mfx_score_src *src, const mfx_score_dst *dst, void *stream);
+
 /* ---------------------------------------------------------------- Q-network training (csrc/qtrain_kernels.hip) */
 /* ValueNet's minibatch step (algo/base.py:123-279, algo/q_learning.py) for the Q network above, f32, on the device:
  * sample rows idx and (idx + 1) % n straight from the replay ring -> y = f32(f64(r) + ((1 - done) f64(q_target[argmax

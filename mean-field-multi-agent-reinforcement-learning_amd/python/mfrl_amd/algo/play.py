@@ -10,6 +10,8 @@
   per step), the replay rows collected by mfrl_amd.replay.RolloutCollector (DQN / MFQ).
 * play_rollout_episodes: the same round for ActorCritic / MFAC -- the rows go into the model's EpisodesBuffer with
   their episode chains (the collector's linked path) and train_rollout() trains on them in place.
+* battle_rollout: an evaluation round (battle) on the device rollout loop for any pairing of models with act_rollout,
+  the outcomes of the episodes kept on the device by mfrl_amd.scoreboard.RolloutScoreboard.
 """
 import math
 import random
@@ -303,3 +305,79 @@ def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, 
     if train:
         print("[INFO] device rollout: {} replay rows, {} episodes finished".format(rows, int(stats[:, 0].sum().item())))
     return max_nums, nums, mean_rewards, total_rewards
+
+
+def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, left_id=None, check_every=25,
+                   board=None):
+    """One evaluation round (battle) on all E envs of `eng` on the device rollout loop: models[g].act_rollout for both
+    groups -- any pairing of DQN / MFQ / AC / MFAC --, BattleBatch.rollout_policy_step, and one
+    RolloutScoreboard.update() per step; no training, no buffers, no host synchronisation inside the loop except one
+    8-byte readback every check_every steps.
+
+    Only each env's first episode counts: every env finishes it within max_steps steps (the rollout's episode cap), so
+    a round is exactly E episodes, as E rounds of battle() are; counting every episode that ends inside a fixed window
+    would over-weight the short ones.  The round stops at max_steps steps, or at the first multiple of check_every
+    steps at which every env has finished its first episode.  eps is not used (act_rollout is greedy for the Q
+    models and samples for the actor-critic ones, as battle() with eps 0 does).  board: a RolloutScoreboard of `eng`
+    with target 1 and ep_cap >= 1 to keep score on, so that its buffers are reused from round to round (battle_eval
+    passes one); None: one is made for this round.
+
+    Returns (max_nums, nums, mean_rewards, total_rewards, outcome) over those E episodes: the first four as play()
+    gives them to Runner.run, summed over envs -- nums read before clear_dead at each episode's last step,
+    total_rewards[g] the episodes' returns, mean_rewards[g] that per step and agent placed (the per-step group sizes
+    are not kept) --; outcome is RolloutScoreboard.finish()'s dict plus "first" (main_wins, oppo_wins, ties, kills,
+    steps of the counted episodes; a tie counts for both sides in Runner.run), "steps_run" and "agent_steps" (the
+    round's agent-steps over all envs, later episodes included)."""
+    from ..scoreboard import MAIN, OPPONENT, TIE, RolloutScoreboard
+    E, G = eng.n_envs, 2
+    for m in models[:G]:
+        if not hasattr(m, "act_rollout"):
+            raise TypeError("battle_rollout: %s has no device rollout forward" % type(m).__name__)
+    if board is not None and (board.eng is not eng or board.target != 1 or board.ep_cap < 1):
+        raise ValueError("battle_rollout: the scoreboard must be this engine's, with target 1 and ep_cap >= 1")
+    check_every = max(int(check_every), 1)
+    left, right = block_positions(map_size)
+    left_id = random.randint(0, 1) if left_id is None else left_id
+    placement = [None, None]
+    placement[left_id], placement[1 - left_id] = left, right
+    eng.reset()
+    eng.rollout_init(placement, max_steps=max_steps, eps=0.0, seed=n_round, stagger=False)
+    if eng.rollout_policy_path() is None:
+        raise RuntimeError("battle_rollout: this rollout plan takes no learned policy (MFX_ROLLOUT_PIPE=1)")
+    eng.rollout_policy_observe()
+    if board is None:
+        board = RolloutScoreboard(eng)
+    board.attach()
+    max_nums = [len(placement[g]) * E for g in range(G)]
+    print("\n\n[*] ROUND #{0}, EPS: {1:.2f} NUMBER: {2} ({3} envs, device rollout)".format(n_round, eps, max_nums, E))
+    t_play = time.time()
+    step_ct = 0
+    while step_ct < max_steps:
+        for g in range(G):
+            models[g].act_rollout(eng, g)
+        eng.rollout_policy_step()
+        board.update()
+        step_ct += 1
+        if step_ct % check_every == 0 and step_ct < max_steps and board.reached() >= E:
+            break
+    out = board.finish()
+    eng.rollout_check()
+    t_play = time.time() - t_play
+    steps_buf = np.empty(E, dtype=np.int64)
+    eng.rollout_copy("agent_steps", steps_buf)
+    eng.sync()
+    out["agent_steps"] = int(steps_buf.sum())
+    first = out["log"][:, 0]
+    if int((out["totals"][:, 0] >= 1).sum()) != E:
+        raise RuntimeError("battle_rollout: %d of %d envs finished an episode in %d steps"
+                           % (int((out["totals"][:, 0] >= 1).sum()), E, step_ct))
+    nums = [int(first["nums"][:, g].sum()) for g in range(G)]
+    total_rewards = [float(first["ret"][:, g].sum()) for g in range(G)]
+    steps = int(first["len"].sum())
+    mean_rewards = [total_rewards[g] / max(steps * len(placement[g]), 1) for g in range(G)]
+    out["first"] = {"main_wins": int((first["winner"] == MAIN).sum()), "oppo_wins": int((first["winner"] == OPPONENT).sum()),
+                    "ties": int((first["winner"] == TIE).sum()),
+                    "kills": [int(first["kill"][:, g].sum()) for g in range(G)], "steps": steps}
+    out["steps_run"] = step_ct
+    print("[TIME] battle {} steps x {} envs: {:.2f} s; first episodes: {}".format(step_ct, E, t_play, out["first"]))
+    return max_nums, nums, mean_rewards, total_rewards, out

@@ -1,0 +1,113 @@
+"""The tournament, battle.py (reference root) without TensorFlow: two trained models, which may be different
+algorithms, play --n_round evaluation rounds; the last line is the reference's WIN_RATE.
+
+    python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --n_round 50 --idx 1999 1999
+    python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --idx 1999 1999     # the device rollout loop
+    python -m mfrl_amd.battle_eval --algo mfac --oppo ac --envs 8192 --act_precision bf16 --idx 1999 1999
+
+Models are loaded from <base_dir>/data/models/<algo>-0 and <base_dir>/data/models/<oppo>-1 at the two --idx steps, as
+the reference does (train_battle saves them there).  --envs 1 is the reference's path unchanged: tools.Runner with
+play.battle and train=False, runner.run(0.0, k, win_cnt=win_cnt).  --envs E > 1 plays every round on the device
+rollout loop (play.battle_rollout): E episodes per round, their outcomes kept on the device by
+mfrl_amd.scoreboard.RolloutScoreboard with Runner.run's own win rule -- kill[i] = max_nums[i] - nums[1 - i], nums read
+before clear_dead; a tie counts for both sides --, so WIN_RATE is over n_round * E episodes.
+"""
+import argparse
+import os
+import time
+
+import torch
+
+import magent
+
+from .algo import spawn_ai, tools
+from .algo.play import battle, battle_rollout
+
+ALGOS = ("ac", "mfac", "mfq", "il")
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--algo", type=str, choices=ALGOS, required=True, help="the main model's algorithm")
+    parser.add_argument("--oppo", type=str, choices=ALGOS, help="the opponent model's algorithm (default: --algo)")
+    parser.add_argument("--n_round", type=int, default=50)
+    parser.add_argument("--render", action="store_true")
+    parser.add_argument("--map_size", type=int, default=40)
+    parser.add_argument("--max_steps", type=int, default=400)
+    parser.add_argument("--idx", nargs="*", help="the saved steps of the two models: A B")
+    parser.add_argument("--envs", type=int, default=1, help="envs per round (>1: the device rollout loop)")
+    parser.add_argument("--act_precision", type=str, choices=["f32", "bf16"], default="f32",
+                        help="the acting forward's matrix operands on the device rollout loop (mfrl_amd.policy)")
+    parser.add_argument("--base_dir", type=str, default=os.getcwd())
+    parser.add_argument("--seed", type=int, default=0, help="torch / numpy / python seed (model initialisation, draws)")
+    parser.add_argument("--untrained", action="store_true",
+                        help="skip load: seeded initial weights (smoke runs and tests)")
+    args = parser.parse_args(argv)
+    if args.oppo is None:
+        args.oppo = args.algo
+    if args.n_round < 1:
+        parser.error("--n_round must be at least 1")
+    if args.envs < 1:
+        parser.error("--envs must be at least 1")
+    if args.max_steps < 1:
+        parser.error("--max_steps must be at least 1")
+    if args.untrained and args.idx:
+        parser.error("--untrained loads nothing: give it or --idx A B, not both")
+    if not args.untrained and (args.idx is None or len(args.idx) != 2):
+        parser.error("--idx takes the two saved steps A B (or give --untrained)")
+    if args.render and args.envs > 1:
+        parser.error("--render draws one env through the drop-in API: --envs 1")
+    if args.act_precision != "f32" and args.envs <= 1:
+        parser.error("--act_precision bf16 is the device rollout loop's acting mode: --envs > 1")
+
+    import random
+
+    import numpy as np
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    random.seed(args.seed)
+    env = magent.GridWorld("battle", map_size=args.map_size)
+    env.set_render_dir(os.path.join(args.base_dir, "examples/battle_model", "build/render"))      # battle.py:41
+    handles = env.get_handles()
+    main_model_dir = os.path.join(args.base_dir, "data/models/{}-0".format(args.algo))
+    oppo_model_dir = os.path.join(args.base_dir, "data/models/{}-1".format(args.oppo))
+    # (no round trains: the replay ring of mfq / il stays empty, so it is made small)
+    models = [spawn_ai(args.algo, None, env, handles[0], args.algo + "-me", args.max_steps, memory_size=1024),
+              spawn_ai(args.oppo, None, env, handles[1], args.oppo + "-opponent", args.max_steps, memory_size=1024)]
+    if not args.untrained:
+        models[0].load(main_model_dir, step=args.idx[0])
+        models[1].load(oppo_model_dir, step=args.idx[1])
+    win_cnt = {"main": 0, "opponent": 0}
+    t0 = time.time()
+    if args.envs == 1:
+        # (battle.py:62 passes render_every=0 whatever --render says; so does this)
+        runner = tools.Runner(None, env, handles, args.map_size, args.max_steps, models, battle, render_every=0)
+        for k in range(args.n_round):
+            runner.run(0.0, k, win_cnt=win_cnt)
+        episodes = args.n_round
+    else:
+        from .battle import BattleBatch
+        from .scoreboard import RolloutScoreboard
+        for m in models:
+            if args.act_precision != "f32":
+                m.act_precision = args.act_precision
+        eng = BattleBatch(args.map_size, args.envs, stream=torch.cuda.current_stream())
+        board = RolloutScoreboard(eng, ep_cap=1, target=1)       # one set of buffers for all rounds
+        steps = 0
+        for k in range(args.n_round):
+            out = battle_rollout(eng, k, args.map_size, args.max_steps, models, eps=0.0, board=board)[4]
+            first = out["first"]
+            win_cnt["main"] += first["main_wins"] + first["ties"]
+            win_cnt["opponent"] += first["oppo_wins"] + first["ties"]
+            steps += out["steps_run"]
+        episodes = args.n_round * args.envs
+        torch.cuda.synchronize()
+        print("[TIME] {} rounds x {} envs: {:.2f} s, {} steps of every env".format(args.n_round, args.envs,
+                                                                                  time.time() - t0, steps))
+    print("\n[*] >>> WIN_RATE: [{0}] {1} / [{2}] {3}".format(args.algo, win_cnt["main"] / episodes, args.oppo,
+                                                           win_cnt["opponent"] / episodes))
+    return win_cnt
+
+
+if __name__ == "__main__":
+    main()
