@@ -122,11 +122,12 @@ int mfx_battle_rollout_step(void *game, int n_steps);
  * steps in one launch.  rollout_step(n) gives identical results for every value.  get: the value in force. */
 int mfx_battle_rollout_set_substeps(void *game, int n_sub);
 int mfx_battle_rollout_get_substeps(void *game, int *n_sub);
-/* names: view, feature, actions, rewards, mean_action, episode_return, stats, agent_steps, group_num, ids, alive.
+/* names: view, feature, actions, rewards, mean_action, episode_return, stats, agent_steps, group_num, ids, alive, rng.
  * ids (int32 [E][G][rowcap]) and alive (uint8 [E][G][rowcap]) are written by mfx_battle_rollout_policy_step only
  * (mfx_battle_rollout_step leaves them alone): row i of group g of env e holds what mfx_battle_get's id / alive
  * getters would report for that member after the step and before clear_dead -- the row order of actions and
- * rewards.  Copyable (rollout_copy / rollout_copy_at), not writable. */
+ * rewards.  Copyable (rollout_copy / rollout_copy_at), not writable.
+ * rng (uint32 [E]): every env's shuffle engine, a minstd state (GridWorld.cc:31, :512); no reset re-seeds it. */
 int mfx_battle_rollout_buffer(void *game, const char *name, int group, void **d_ptr, size_t *bytes);
 int mfx_battle_rollout_copy(void *game, const char *name, int group, void *dst, size_t bytes);
 /* bytes [offset, offset + bytes) of a rollout buffer (e.g. one env's rows), async on the engine stream */
@@ -420,6 +421,79 @@ typedef struct mfx_score_dst {
 int mfx_score_sizes(int n_envs, int64_t ep_cap, size_t bytes[5]);
 int mfx_score_attach(const mfx_score_src *src, const mfx_score_dst *dst, void *stream);
 int mfx_score_update(const mfx_score_src *src, const mfx_score_dst *dst, void *stream);
+
+/* ---------------------------------------------------------------- part 8: watched-env trace (csrc/trace_kernels.hip) */
+/* The recorder of the device rollout loop: per step, for each of K watched envs (1 <= K <= MFX_TRACE_MAX_ENVS), the
+ * rows that let a one-env engine re-run the env from the round's start and prove the re-run right
+ * (mfrl_amd.recorder: RolloutRecorder, replay).  Two groups only.  The sources are the rollout buffers of
+ * mfx_battle_rollout_buffer, or any device arrays of the same layout, 16-byte aligned (alive: 4-byte).
+ * A round starts from reset + placement, but an env's shuffle engine (the minstd state behind the attack order,
+ * GridWorld.cc:507-512) is never re-seeded by a reset: it runs on from round to round.  So the state it has at attach
+ * ("rng" of mfx_battle_rollout_buffer) is part of the trace, and a re-run starts from it (the "seed" config key).
+ *
+ * One launch per step, after the step.  A learned policy's step reads the action buffer and never writes it
+ * (agent_phase / big_env_step with kExt: csrc/battle/rollout.inc, rollout_big.inc), so the actions the step acted with
+ * are still there behind it; group_num is not -- clear_dead and a restart rewrite it inside the step -- so the group
+ * sizes of before the step are carried from attach / the previous update, as the scorekeeper carries n_cur.  Hence no
+ * begin / end pair: nothing else the record needs is gone after the step.
+ *   mfx_trace_attach   after the policy observe, before the first policy step.  h_envs: the K watched env indices on
+ *                      the host, each in [0, n_envs), no duplicate (refused otherwise); they are copied to dst->envs on
+ *                      `stream`.  Zeroes state; carry[0][k] = {group_num[e][0], group_num[e][1], (int64)stats[e][0],
+ *                      agent_steps[e]}; seeds[k] = rng[e]; a group size outside [0, rowcap] sets MFX_TRACE_ERR_COUNT.
+ *   mfx_trace_update   exactly once after every mfx_battle_rollout_policy_step; `step` = updates since attach (0, 1,
+ *                      ...: the host knows it without a readback).  step >= cap_steps: MFX_TRACE_FULL is set and nothing
+ *                      else is written.  Otherwise, for watched env k (e = envs[k]) with {n0, n1, ep, steps0} =
+ *                      carry[step & 1][k]:
+ *                      guard   agent_steps[e] - steps0 must be n0 + n1, else MFX_TRACE_ERR_STEP (a step was not
+ *                              recorded, or was recorded twice); (int64)stats[e][0] - ep must be 0 or 1, else
+ *                              MFX_TRACE_ERR_EPISODE; n0, n1 and the new group sizes must lie in [0, rowcap], else
+ *                              MFX_TRACE_ERR_COUNT.  A failed guard sets its bits in the sticky word and the record's
+ *                              valid word to 0; the carry is taken afresh either way.
+ *                      head[step][k] = {valid, n0, n1, ep, (int64)stats[e][0], agent_steps[e]} (MFX_TRACE_HEAD words);
+ *                      actions / ids / rewards / alive [step][k][g][0 .. rowcap) = the source rows [e][g][0 .. rowcap)
+ *                      verbatim, stale entries at and past n[g] included (no address depends on n);
+ *                      carry[(step + 1) & 1][k] = {group_num[e][0], group_num[e][1], (int64)stats[e][0],
+ *                      agent_steps[e]}; state[0] = step + 1.
+ *                      An envs[k] outside [0, n_envs) on the device (the host refused it: a corrupted list) sets
+ *                      MFX_TRACE_ERR_ENV, valid = 0, and no row is read or written.
+ * One workgroup per (watched env, group); the lanes move the int32 / float rows as 16-byte vectors (rowcap is a multiple
+ * of 4) and the alive row as 16-byte vectors when rowcap is a multiple of 16, else as dwords; the group-0 workgroup
+ * writes the head and the carry of the other parity, which no workgroup of the launch reads.  Plain stores, one integer
+ * atomic OR on the error word, no float atomics; nothing depends on the launch order.  Nothing synchronises and nothing
+ * is read back.  Nothing is written outside dst's arrays: every offset is a function of step < cap_steps, k < K, g < 2
+ * and the row index < rowcap alone. */
+enum { MFX_TRACE_MAX_ENVS = 16, MFX_TRACE_HEAD = 6, MFX_TRACE_CARRY = 4 };
+enum { MFX_TRACE_VALID = 0, MFX_TRACE_N = 1, MFX_TRACE_EP_BEFORE = 3, MFX_TRACE_EP_AFTER = 4, MFX_TRACE_STEPS = 5 };
+enum { MFX_TRACE_ERR_STEP = 1, MFX_TRACE_ERR_EPISODE = 2, MFX_TRACE_ERR_COUNT = 4, MFX_TRACE_FULL = 8,
+       MFX_TRACE_ERR_ENV = 16 };
+typedef struct mfx_trace_src {
+    const int32_t *group_num;             /* [E][2] */
+    const uint8_t *alive;                 /* [E][2][rowcap] */
+    const double *stats;                  /* [E][4] */
+    const int64_t *agent_steps;           /* [E] */
+    const int32_t *actions;               /* [E][2][rowcap] */
+    const int32_t *ids;                   /* [E][2][rowcap] */
+    const float *rewards;                 /* [E][2][rowcap] */
+    const uint32_t *rng;                  /* [E] */
+    int32_t n_envs, n_groups, rowcap;     /* rowcap: a multiple of 4 */
+} mfx_trace_src;
+typedef struct mfx_trace_dst {
+    int32_t *envs;                        /* [K] watched env indices (device; written by attach) */
+    int64_t *carry;                       /* [2][K][MFX_TRACE_CARRY], by step parity */
+    int64_t *head;                        /* [cap_steps][K][MFX_TRACE_HEAD] */
+    int32_t *actions;                     /* [cap_steps][K][2][rowcap] */
+    int32_t *ids;                         /* [cap_steps][K][2][rowcap] */
+    float *rewards;                       /* [cap_steps][K][2][rowcap] */
+    uint8_t *alive;                       /* [cap_steps][K][2][rowcap] */
+    int64_t *state;                       /* [2]: steps recorded, the sticky error word */
+    uint32_t *seeds;                      /* [K] the watched envs' shuffle-engine states at attach */
+    int64_t cap_steps;                    /* >= 1 */
+    int32_t n_watch;                      /* K */
+} mfx_trace_dst;
+/* bytes of envs, carry, head, actions, ids, rewards, alive, state, seeds (host) */
+int mfx_trace_sizes(int n_watch, int rowcap, int64_t cap_steps, size_t bytes[9]);
+int mfx_trace_attach(const mfx_trace_src *src, const mfx_trace_dst *dst, const int32_t *h_envs, void *stream);
+int mfx_trace_update(const mfx_trace_src *src, const mfx_trace_dst *dst, int64_t step, void *stream);
 
 /* ---------------------------------------------------------------- Q-network training (csrc/qtrain_kernels.hip) */
 /* ValueNet's minibatch step (algo/base.py:123-279, algo/q_learning.py) for the Q network above, f32, on the device:

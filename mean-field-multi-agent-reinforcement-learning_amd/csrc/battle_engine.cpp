@@ -1784,6 +1784,7 @@ public:
         else if (!strcmp(name, "stats")) { *ptr = ra.stats; *bytes = (size_t)E * 4 * 8; }
         else if (!strcmp(name, "agent_steps")) { *ptr = ra.agent_steps; *bytes = (size_t)E * 8; }
         else if (!strcmp(name, "group_num")) { *ptr = s.grp_n; *bytes = (size_t)E * G * 4; }
+        else if (!strcmp(name, "rng")) { *ptr = s.rng; *bytes = (size_t)E * 4; }   // the envs' shuffle engines (minstd states)
         else return fail("unknown rollout buffer %s", name);
         return 0;
     }

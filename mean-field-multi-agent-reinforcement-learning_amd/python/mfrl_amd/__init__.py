@@ -4,6 +4,7 @@
     mfrl_amd.battle   BattleBatch: E envs in HBM, fused rollout step (bench path)
     mfrl_amd.ising    Ising lattice + tabular MF-Q (main_MFQ_Ising.py) on device
     mfrl_amd.mf       mean-action pooling, MF-Q target, MF-AC discounted returns
+    mfrl_amd.recorder watched envs of the device rollout loop: trace on the device, replay and frames behind the round
 """
 import ctypes
 import os

@@ -12,6 +12,8 @@
   their episode chains (the collector's linked path) and train_rollout() trains on them in place.
 * battle_rollout: an evaluation round (battle) on the device rollout loop for any pairing of models with act_rollout,
   the outcomes of the episodes kept on the device by mfrl_amd.scoreboard.RolloutScoreboard.
+* The three device-loop rounds take recorder=: a mfrl_amd.recorder.RolloutRecorder that records a few watched envs, to
+  be re-run and rendered behind the round (mfrl_amd.recorder.replay).
 """
 import math
 import random
@@ -200,7 +202,8 @@ def play_batched(eng, n_round, map_size, max_steps, models, print_every=50, eps=
     return max_nums, nums, mean_rewards, total_rewards
 
 
-def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, train=False, left_id=None):
+def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, train=False, left_id=None,
+                 recorder=None):
     """One round of max_steps steps on all E envs of `eng` on the device rollout loop: ValueNet.act_rollout for both
     groups, BattleBatch.rollout_policy_step, and -- with train -- group 0's replay rows collected by a
     mfrl_amd.replay.RolloutCollector around every step, then models[0].train().  No host synchronisation inside
@@ -232,10 +235,11 @@ def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=
         return col
 
     return _rollout_round("play_rollout", eng, n_round, map_size, max_steps, models, eps, train, left_id, collector,
-                          models[0].train)
+                          models[0].train, recorder)
 
 
-def play_rollout_episodes(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, train=False, left_id=None):
+def play_rollout_episodes(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, train=False, left_id=None,
+                          recorder=None):
     """play_rollout for the actor-critic models (ActorCritic, MFAC: act_rollout and an EpisodesBuffer): the same
     round -- max_steps steps of every env on the device rollout loop, an env that ends early restarting inside the
     loop, the statistics read once at the end from the rollout's buffers -- with group 0's rows collected into
@@ -254,12 +258,14 @@ def play_rollout_episodes(eng, n_round, map_size, max_steps, models, print_every
         raise TypeError("play_rollout_episodes: %s does not train from an EpisodesBuffer (AC / MFAC only; play_rollout "
                         "trains DQN / MFQ)" % type(models[0]).__name__)
     return _rollout_round("play_rollout_episodes", eng, n_round, map_size, max_steps, models, eps, train, left_id,
-                          lambda: models[0].rollout_collector(eng, 0), models[0].train_rollout)
+                          lambda: models[0].rollout_collector(eng, 0), models[0].train_rollout, recorder)
 
 
-def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, left_id, collector, train_fn):
+def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, left_id, collector, train_fn,
+                   recorder=None):
     """The round of play_rollout / play_rollout_episodes: collector() gives group 0's RolloutCollector, train_fn()
-    trains models[0] on what it collected."""
+    trains models[0] on what it collected.  recorder: a mfrl_amd.recorder.RolloutRecorder of `eng` that records its
+    watched envs over the round (one more launch per step; recorder.trace holds the round's trace afterwards), or None."""
     E, G = eng.n_envs, 2
     left, right = block_positions(map_size)
     left_id = random.randint(0, 1) if left_id is None else left_id
@@ -271,6 +277,8 @@ def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, 
         raise RuntimeError("%s: this rollout plan takes no learned policy (MFX_ROLLOUT_PIPE=1)" % name)
     eng.rollout_policy_observe()
     col = collector() if train else None
+    if recorder is not None:
+        recorder.attach(map_size, max_steps, placement)
     max_nums = [len(placement[g]) * E for g in range(G)]
     print("\n\n[*] ROUND #{0}, EPS: {1:.2f} NUMBER: {2} ({3} envs, device rollout)".format(n_round, eps, max_nums, E))
     t_play = time.time()
@@ -282,7 +290,11 @@ def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, 
         eng.rollout_policy_step()
         if col is not None:
             col.end()
+        if recorder is not None:
+            recorder.update()
     rows = col.finish() if col is not None else 0
+    if recorder is not None:
+        recorder.finish()
     eng.rollout_check()
     t_play = time.time() - t_play
     stats = torch.empty((E, 4), dtype=torch.float64, device="cuda")
@@ -308,7 +320,7 @@ def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, 
 
 
 def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=1.0, left_id=None, check_every=25,
-                   board=None):
+                   board=None, recorder=None):
     """One evaluation round (battle) on all E envs of `eng` on the device rollout loop: models[g].act_rollout for both
     groups -- any pairing of DQN / MFQ / AC / MFAC --, BattleBatch.rollout_policy_step, and one
     RolloutScoreboard.update() per step; no training, no buffers, no host synchronisation inside the loop except one
@@ -320,7 +332,8 @@ def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, ep
     steps at which every env has finished its first episode.  eps is not used (act_rollout is greedy for the Q
     models and samples for the actor-critic ones, as battle() with eps 0 does).  board: a RolloutScoreboard of `eng`
     with target 1 and ep_cap >= 1 to keep score on, so that its buffers are reused from round to round (battle_eval
-    passes one); None: one is made for this round.
+    passes one); None: one is made for this round.  recorder: a mfrl_amd.recorder.RolloutRecorder of `eng` that records
+    its watched envs over the round (one more launch per step); the outcome then holds the round's "trace".
 
     Returns (max_nums, nums, mean_rewards, total_rewards, outcome) over those E episodes: the first four as play()
     gives them to Runner.run, summed over envs -- nums read before clear_dead at each episode's last step,
@@ -348,6 +361,8 @@ def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, ep
     if board is None:
         board = RolloutScoreboard(eng)
     board.attach()
+    if recorder is not None:
+        recorder.attach(map_size, max_steps, placement)
     max_nums = [len(placement[g]) * E for g in range(G)]
     print("\n\n[*] ROUND #{0}, EPS: {1:.2f} NUMBER: {2} ({3} envs, device rollout)".format(n_round, eps, max_nums, E))
     t_play = time.time()
@@ -357,10 +372,14 @@ def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, ep
             models[g].act_rollout(eng, g)
         eng.rollout_policy_step()
         board.update()
+        if recorder is not None:
+            recorder.update()
         step_ct += 1
         if step_ct % check_every == 0 and step_ct < max_steps and board.reached() >= E:
             break
     out = board.finish()
+    if recorder is not None:
+        out["trace"] = recorder.finish()
     eng.rollout_check()
     t_play = time.time() - t_play
     steps_buf = np.empty(E, dtype=np.int64)

@@ -4,13 +4,16 @@ algorithms, play --n_round evaluation rounds; the last line is the reference's W
     python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --n_round 50 --idx 1999 1999
     python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --idx 1999 1999     # the device rollout loop
     python -m mfrl_amd.battle_eval --algo mfac --oppo ac --envs 8192 --act_precision bf16 --idx 1999 1999
+    python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --watch 0 63 --idx 1999 1999    # + frames of two envs
 
 Models are loaded from <base_dir>/data/models/<algo>-0 and <base_dir>/data/models/<oppo>-1 at the two --idx steps, as
 the reference does (train_battle saves them there).  --envs 1 is the reference's path unchanged: tools.Runner with
 play.battle and train=False, runner.run(0.0, k, win_cnt=win_cnt).  --envs E > 1 plays every round on the device
 rollout loop (play.battle_rollout): E episodes per round, their outcomes kept on the device by
 mfrl_amd.scoreboard.RolloutScoreboard with Runner.run's own win rule -- kill[i] = max_nums[i] - nums[1 - i], nums read
-before clear_dead; a tie counts for both sides --, so WIN_RATE is over n_round * E episodes.
+before clear_dead; a tie counts for both sides --, so WIN_RATE is over n_round * E episodes.  --watch ENV [ENV ...]
+records those envs of the first --watch_rounds rounds on the device (mfrl_amd.recorder), re-runs each one's first episode
+on the one-env engine and writes the reference's frame files under <render dir>/round_<k>/env_<e>/.
 """
 import argparse
 import os
@@ -42,6 +45,10 @@ def main(argv=None):
     parser.add_argument("--seed", type=int, default=0, help="torch / numpy / python seed (model initialisation, draws)")
     parser.add_argument("--untrained", action="store_true",
                         help="skip load: seeded initial weights (smoke runs and tests)")
+    parser.add_argument("--watch", type=int, nargs="+", metavar="ENV",
+                        help="with --envs > 1: record these envs (at most 16) on the device rollout loop and write the "
+                             "frames of their first episode")
+    parser.add_argument("--watch_rounds", type=int, default=1, help="rounds --watch records (the first ones)")
     args = parser.parse_args(argv)
     if args.oppo is None:
         args.oppo = args.algo
@@ -59,6 +66,16 @@ def main(argv=None):
         parser.error("--render draws one env through the drop-in API: --envs 1")
     if args.act_precision != "f32" and args.envs <= 1:
         parser.error("--act_precision bf16 is the device rollout loop's acting mode: --envs > 1")
+    if args.watch is not None:
+        from .recorder import check_watch
+        if args.envs <= 1:
+            parser.error("--watch records envs of the device rollout loop: --envs > 1")
+        if args.watch_rounds < 1:
+            parser.error("--watch_rounds must be at least 1")
+        try:
+            check_watch(args.watch, args.envs)
+        except ValueError as err:
+            parser.error(str(err))
 
     import random
 
@@ -67,7 +84,8 @@ def main(argv=None):
     np.random.seed(args.seed)
     random.seed(args.seed)
     env = magent.GridWorld("battle", map_size=args.map_size)
-    env.set_render_dir(os.path.join(args.base_dir, "examples/battle_model", "build/render"))      # battle.py:41
+    render_dir = os.path.join(args.base_dir, "examples/battle_model", "build/render")
+    env.set_render_dir(render_dir)                                                                # battle.py:41
     handles = env.get_handles()
     main_model_dir = os.path.join(args.base_dir, "data/models/{}-0".format(args.algo))
     oppo_model_dir = os.path.join(args.base_dir, "data/models/{}-1".format(args.oppo))
@@ -93,9 +111,19 @@ def main(argv=None):
                 m.act_precision = args.act_precision
         eng = BattleBatch(args.map_size, args.envs, stream=torch.cuda.current_stream())
         board = RolloutScoreboard(eng, ep_cap=1, target=1)       # one set of buffers for all rounds
+        rec = None
+        if args.watch is not None:
+            from .recorder import RolloutRecorder, replay
+            rec = RolloutRecorder(eng, args.watch, args.max_steps)
         steps = 0
         for k in range(args.n_round):
-            out = battle_rollout(eng, k, args.map_size, args.max_steps, models, eps=0.0, board=board)[4]
+            watching = rec is not None and k < args.watch_rounds
+            out = battle_rollout(eng, k, args.map_size, args.max_steps, models, eps=0.0, board=board,
+                                 recorder=rec if watching else None)[4]
+            if watching:         # behind the round: nothing of the one-env engine runs beside the rollout loop
+                for j, e in enumerate(args.watch):
+                    done = replay(out["trace"], j, render_dir=os.path.join(render_dir, "round_%d" % k), episodes=1)
+                    print("[WATCH] round {} env {}: {} steps in {}".format(k, e, done["steps"], done["dir"]))
             first = out["first"]
             win_cnt["main"] += first["main_wins"] + first["ties"]
             win_cnt["opponent"] += first["oppo_wins"] + first["ties"]

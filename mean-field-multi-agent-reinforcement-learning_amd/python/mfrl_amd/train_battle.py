@@ -6,6 +6,7 @@
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --train_backend hip ...   # + the HIP training step
     python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes ...   # the device rollout loop (ac / mfac)
     python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes --ac_train_backend hip ...   # + the HIP step
+    python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --render --watch 0 63 ...   # + frames of two envs
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -63,6 +64,9 @@ def main(argv=None):
     parser.add_argument("--ac_train_backend", type=str, choices=["torch", "hip"], default="torch",
                         help="ac / mfac: train() / train_rollout() on torch autograd or on the hand-written HIP "
                              "training step (mfrl_amd.actrain), with or without --rollout_episodes")
+    parser.add_argument("--watch", type=int, nargs="+", metavar="ENV",
+                        help="with --rollout / --rollout_episodes: record these envs (at most 16) on the rounds --render "
+                             "marks and write their frames (mfrl_amd.recorder)")
     args = parser.parse_args(argv)
     if args.ac_train_backend == "hip" and args.algo not in ("ac", "mfac"):
         parser.error("--ac_train_backend hip trains the actor-critic network: --algo ac or mfac (mfq / il: "
@@ -83,9 +87,20 @@ def main(argv=None):
     if args.rollout and args.algo not in ("mfq", "il"):
         parser.error("--rollout collects into a MemoryGroup: --algo mfq or il (ac / mfac train from an EpisodesBuffer: "
                      "--rollout_episodes)")
+    if args.watch is not None:
+        from .recorder import check_watch
+        if not (args.rollout or args.rollout_episodes):
+            parser.error("--watch records envs of the device rollout loop: --rollout or --rollout_episodes")
+        try:
+            check_watch(args.watch, args.envs)
+        except ValueError as err:
+            parser.error(str(err))
+        if not args.render:
+            parser.error("--watch writes frames on the rounds --render marks: give --render too")
 
     env = magent.GridWorld("battle", map_size=args.map_size)
-    env.set_render_dir(os.path.join(args.base_dir, "examples/battle_model", "build/render"))  # train_battle.py:87
+    render_dir = os.path.join(args.base_dir, "examples/battle_model", "build/render")
+    env.set_render_dir(render_dir)                                                            # train_battle.py:87
     handles = env.get_handles()
     log_dir = os.path.join(args.base_dir, "data/tmp")
     model_dir = os.path.join(args.base_dir, "data/models/{}".format(args.algo))
@@ -105,12 +120,23 @@ def main(argv=None):
     if args.envs > 1:
         from .battle import BattleBatch
         eng = BattleBatch(args.map_size, args.envs, stream=torch.cuda.current_stream())
+        rec = None
+        if args.watch is not None:
+            from .recorder import RolloutRecorder, replay
+            rec = RolloutRecorder(eng, args.watch, args.max_steps)
 
         def play_handle(env, n_round, map_size, max_steps, handles, models, print_every, eps=1.0, render=False,
                         train=False):
             loop = (play_rollout if args.rollout else play_rollout_episodes if args.rollout_episodes
                     else play_batched)
-            return loop(eng, n_round, map_size, max_steps, models, print_every, eps, train)
+            if rec is None or not render:
+                return loop(eng, n_round, map_size, max_steps, models, print_every, eps, train)
+            res = loop(eng, n_round, map_size, max_steps, models, print_every, eps, train, recorder=rec)
+            for j, e in enumerate(args.watch):       # behind the round: nothing of it runs beside the rollout loop
+                done = replay(rec.trace, j, render_dir=os.path.join(render_dir, "round_%d" % n_round))
+                print("[WATCH] round {} env {}: {} steps, {} episodes in {}".format(n_round, e, done["steps"],
+                                                                                    done["episodes"], done["dir"]))
+            return res
     runner = tools.Runner(None, env, handles, args.map_size, args.max_steps, models, play_handle,
                           render_every=args.save_every if args.render else 0, save_every=args.save_every, tau=0.01,
                           log_name=args.algo, log_dir=log_dir, model_dir=model_dir, train=True)
