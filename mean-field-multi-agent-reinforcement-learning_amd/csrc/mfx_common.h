@@ -8,6 +8,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
@@ -31,6 +32,14 @@ inline int fail(const char* fmt, ...) {
     set_last_error(buf);
     return -1;
 }
+
+// The MFX_* environment switches (A/B runs, sweeps, tests): a switch's integer value, dflt when it is not set, and
+// the same read as a flag (0 = off).  Read where the caller stands, never cached: tests change them between engines.
+inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt) != 0; }
 
 struct HipFailure : std::runtime_error {
     using std::runtime_error::runtime_error;

@@ -1,4 +1,4 @@
-"""A learned policy's rollout steps on the large-env plans (mfx_battle_rollout_policy_step on every ro_big plan:
+"""A learned policy's rollout steps on the large-env plans (mfx_battle_rollout_policy_step on every HBM plan:
 k_rollout_big<ext> + k_observe_items on the engine's stream): large envs (state in HBM, clear_dead renumbers the
 slots), batches of few LDS-sized envs (the env staged in LDS for its step; rollout_step's own form is the queue
 kernel, pipelined for few envs), and both interleaved with rollout_step.

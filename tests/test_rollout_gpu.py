@@ -1149,3 +1149,111 @@ def test_rollout_two_engines_two_streams(E):
         dumps.append(_dump_rollout(eng, E, N))
     for (k, x), (_, y) in zip(dumps[0], dumps[1]):
         assert torch.equal(x, y), k
+
+
+def _plan_tuple(eng):
+    """The public face of an engine's rollout plan: (rollout_step's kernels, rollout_policy_step's kernels or -1,
+    reward-sum lanes of 64 and of 65 agents, steps per launch chosen by the engine, (grid, LDS bytes))."""
+    paths = type(eng).PATHS
+    pol = eng.rollout_policy_path()
+    eng.rollout_substeps(0)
+    return (paths.index(eng.rollout_path()), -1 if pol is None else paths.index(pol), eng.rollout_sum_lanes(64),
+            eng.rollout_sum_lanes(65), eng.get_substeps(), eng.rollout_info())
+
+
+_PLAN_SWITCHES = ("MFX_SMALL_E", "MFX_ROLLOUT_PIPE", "MFX_FEW_PIPE", "MFX_BIG_FUSED")
+
+
+def _set_plan_switches(monkeypatch, switches):
+    for k in _PLAN_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in switches.items():
+        monkeypatch.setenv(k, v)
+
+
+# shape: (map size, agents a side, envs); "generic" is test_rollout_generic_shape_matches_oracle's config and size
+_PLAN_SHAPES = {"small": (24, 18, 3), "large": (200, 1250, 2), "generic": (32, 40, 2)}
+# (case, shape, switches, path, policy path, lanes(64), lanes(65), steps per launch, grid, LDS bytes); at these env
+# counts every plan's grid is its env count, whatever the device's compute units
+_PLAN_TABLE = [
+    ("fused", "small", {"MFX_SMALL_E": "0", "MFX_ROLLOUT_PIPE": "0"}, 0, 0, 64, 256, 2, 3, 13264),
+    ("pipe", "small", {"MFX_SMALL_E": "0", "MFX_ROLLOUT_PIPE": "1"}, 1, -1, 64, 256, 1, 3, 13264),
+    ("few_pipe", "small", {}, 3, 2, 64, 512, 1024, 3, 9856),
+    ("big_queue_few", "small", {"MFX_FEW_PIPE": "0"}, 3, 2, 512, 512, 20, 3, 9856),
+    ("big_streams", "small", {"MFX_BIG_FUSED": "0"}, 2, 2, 512, 512, 1, 3, 9856),
+    ("big_queue_large", "large", {}, 3, 2, 512, 512, 20, 2, 79120),
+    # (not the Battle shape and LDS-sized: never a few-env batch, so k_rollout whatever the env count)
+    ("generic", "generic", {}, 0, 0, 64, 256, 2, 2, 17760),
+]
+
+
+def _plan_engine(shape):
+    import torch
+    from mfrl_amd.battle import BattleBatch
+    map_size, n_side, E = _PLAN_SHAPES[shape]
+    config = _generic_config(map_size) if shape == "generic" else "battle"
+    eng = BattleBatch(map_size, E, config=config, stream=torch.cuda.current_stream())
+    return eng, bd.block_positions(map_size, n_side)
+
+
+@pytest.mark.parametrize("case", _PLAN_TABLE, ids=[c[0] for c in _PLAN_TABLE])
+def test_rollout_plan_table(case, monkeypatch):
+    """What rollout_init plans for each plan of the engine (Fused, Pipe, FewPipe, BigQueue, BigStreams) at the
+    smallest shapes that reach it: the kernels of rollout_step and of the policy steps, the reward-sum lanes, the
+    steps per launch the engine chooses, the grid and the LDS bytes; then three steps on that plan run clean."""
+    name, shape, switches, path, pol, l64, l65, sub, grid, lds = case
+    _set_plan_switches(monkeypatch, switches)
+    eng, placement = _plan_engine(shape)
+    eng.rollout_init(placement, max_steps=400, eps=0.2, seed=5, stagger=False)
+    got = _plan_tuple(eng)
+    print("plan", name, got)
+    assert got == (path, pol, l64, l65, sub, (grid, lds)), (name, got)
+    eng.rollout_step(3)
+    eng.rollout_check()
+
+
+def test_rollout_reinit_takes_the_new_plan(monkeypatch):
+    """rollout_init on an engine that was on the observation/step pipeline (MFX_ROLLOUT_PIPE=1) plans afresh: with
+    the defaults restored, the second rollout_init gives a fresh engine's plan (the same steps per launch, no
+    re-plan per call) and five single steps give a fresh engine's actions, rewards, views and features bit for bit.
+    (Before the plan became one explicit member the pipeline's flag outlived the second rollout_init: the engine
+    then reported 1 step per launch where a fresh one reports 1024, and planned again on every call.)"""
+    import torch
+    shape = "small"
+    _, N, E = _PLAN_SHAPES[shape]
+    _set_plan_switches(monkeypatch, {"MFX_SMALL_E": "0", "MFX_ROLLOUT_PIPE": "1"})
+    eng, placement = _plan_engine(shape)
+    eng.rollout_init(placement, max_steps=400, eps=0.3, seed=11, stagger=False)
+    assert eng.rollout_path() == "k_rollout_obs+k_rollout"
+    eng.rollout_step(3)
+    eng.rollout_check()
+    _set_plan_switches(monkeypatch, {})
+    fresh, _ = _plan_engine(shape)
+    for e in (eng, fresh):
+        e.rollout_init(placement, max_steps=400, eps=0.3, seed=11, stagger=False)
+    want = _plan_tuple(fresh)
+    got = _plan_tuple(eng)
+    print("reinit plan", got, "fresh", want)
+    assert got == want
+
+    def outputs(e):      # rows < N: the rows every env wrote at its first step after rollout_init (as _dump_rollout)
+        rc, out = e.rowcap, []
+        for nm, dt in (("actions", torch.int32), ("rewards", torch.float32)):
+            x = torch.empty(E * 2 * rc, dtype=dt, device="cuda")
+            e.rollout_copy(nm, x)
+            out.append((nm, x.view(E, 2, rc)[:, :, :N].contiguous()))
+        for g in range(2):
+            for nm, w in (("view", 13 * 13 * 7), ("feature", 34)):
+                x = torch.empty(E * rc * w, dtype=torch.float32, device="cuda")
+                e.rollout_copy(nm, x, group=g)
+                out.append(("%s%d" % (nm, g), x.view(E, rc, w)[:, :N].contiguous()))
+        e.sync()
+        return [(k, v.view(torch.uint8)) for k, v in out]
+
+    for t in range(5):
+        for e in (eng, fresh):
+            e.rollout_step(1)
+        for (k, x), (_, y) in zip(outputs(eng), outputs(fresh)):
+            assert torch.equal(x, y), (t, k)
+    for e in (eng, fresh):
+        e.rollout_check()
