@@ -190,6 +190,45 @@ int mfx_ising_mfq_run_stream(void *handle, int T, double temperature, double lr,
                              double act_rate, unsigned seed0, int episodes, double *q, double *order, int32_t *n_up,
                              int32_t *steps);
 
+/* ---------------------------------------------------------------- part 3b: Ising trace, sweep, Metropolis
+ * The trace: next to order / n_up, every executed step t < steps[r] of replica r also gives
+ *   rsum[r][t] = sum(reward) of the step (main_MFQ_Ising.py:158).  Every reward is a multiple of 0.5 with
+ *                |reward| <= K / 2, so the sum is exact in any order;
+ *   mse[r][t]  = sum over the step's act_group of (Q_new[i] - target[st_i][act_i])^2, over N (:125-133): Q_new the
+ *                entry just updated, st_i the agent's up-neighbour count on the old spins,
+ *                target[s][a] = (a ? 1 : -1) (2 s - K) / 2 -- at K = 4 the script's reward_target table (:77-81).
+ * Summation order of the mse (the script adds in act_group order; the device has only the group's mask): the
+ * workgroup has B = 64 ceil(N / 64) <= 1024 lanes; lane l adds the terms of its own agents l, l + B, ... in ascending
+ * index; an xor butterfly with masks 1, 2, 4, 8, 16, 32 runs over each wave's 64 lanes (v = v + v[lane ^ m]); lane 0
+ * adds the waves' partials in wave order and divides by (double) N.  Single IEEE float64 operations, no
+ * floating-point atomics: bitwise reproducible (tests/ising_trace_ref.py restates it).  Against the script's order
+ * the mse differs by at most 2 N 2^-53 of itself.
+ * Rows t >= steps[r] of rsum / mse (and, from mfx_ising_mfq_run_sweep, of order) read as NaN. */
+/* mfx_ising_mfq_run with the trace and, optional, a clamp temperature per replica: temps [R] (null: `temperature`),
+ * every entry finite and above zero.  rsum, mse [R][T] host, nullable. */
+int mfx_ising_mfq_run_trace(void *handle, int T, double temperature, const double *temps, double lr,
+                            double decay_rate, int decay_gap, const double *u, const uint32_t *mask, unsigned seed,
+                            double *q, double *order, int32_t *n_up, int32_t *steps, double *rsum, double *mse);
+/* A temperature sweep in one launch (single episode, the device's numpy streams): n_streams streams
+ * RandomState(seed0 + s) are generated and walked once; replica r runs main_MFQ_Ising.py at temps[r] on stream
+ * stream_of[r] -- its words, step offsets, act_group masks and env.reset spins -- as the script run with one seed at
+ * several -t.  stream_of null: stream r, and n_streams must equal the handle's replicas.  Returns -1 with a message
+ * on a temperature that is not finite and above zero or a stream_of entry outside [0, n_streams); temps has the
+ * handle's R entries.  Outputs host, nullable except q: q [R][N][K+1][2], order / rsum / mse [R][T], n_up [R][T],
+ * steps [R]. */
+int mfx_ising_mfq_run_sweep(void *handle, int T, const double *temps, const int32_t *stream_of, int n_streams,
+                            unsigned seed0, double lr, double decay_rate, int decay_gap, double act_rate, double *q,
+                            double *order, int32_t *n_up, int32_t *steps, double *rsum, double *mse);
+/* Metropolis baseline from the current spins, 4-neighbour lattices of even side >= 4 only (-1 with a message
+ * otherwise): per sweep the sites of even row + column, then the odd ones; site i of replica r with `a` neighbours
+ * equal to it flips when u < acc[r][a], acc [R][5] host values in [0, 1] (no exp() on the device), u the Philox draw
+ * of counter (i, sweep, r, 0x5EED2) under key (seed, 0xA511E9B3), 53 bits as the MF-Q draws (whose fourth counter
+ * word is 0x5EED1).  order, n_up [R][sweeps] after each sweep; the spins are updated in place. */
+int mfx_ising_mc_run(void *handle, int sweeps, const double *acc, unsigned seed, double *order, int32_t *n_up);
+/* Measurement: record event `which` (0 start, 1 stop) on the handle's stream; the milliseconds between the two. */
+int mfx_ising_mark(void *handle, int which);
+int mfx_ising_marked_ms(void *handle, float *ms);
+
 /* ---------------------------------------------------------------- part 4: mean-field kernels */
 /* senario_battle.py:141 -- d_acts [B][rowcap], d_counts [B] -> d_out [B][n_action] float64, 1 <= n_action <= 256.
  * Row b pools its first n = min(d_counts[b], rowcap) slots (a negative count reads as 0; the row-list kernels cap

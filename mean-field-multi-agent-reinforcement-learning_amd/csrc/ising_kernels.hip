@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "ising_kernels.h"
+#include "ising_philox.h"
 
 namespace mfx {
 
@@ -63,23 +64,6 @@ __global__ void __launch_bounds__(1024) k_ising_step(int N, int K, const int16_t
         const int down = N - cnt;
         order[r] = (double)(cnt > down ? cnt - down : down - cnt) / ((double)N + 0.0);
     }
-}
-
-// ------------------------------------------------------------------ Philox 4x32-10 (perf mode)
-__device__ __forceinline__ void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-__device__ __forceinline__ double philox_uniform(uint32_t seed, uint32_t rep, uint32_t t, uint32_t i) {
-    uint32_t c[4] = {i, t, rep, 0x5EED1u};
-    philox(c, seed, 0xA511E9B3u);
-    const uint64_t bits = ((uint64_t)(c[0] >> 5) << 26) | (c[1] >> 6);   // 53 bits, like random_sample
-    return (double)bits * (1.0 / 9007199254740992.0);
 }
 
 // ------------------------------------------------------------------ numpy's legacy MT19937 stream
@@ -285,18 +269,47 @@ __global__ void __launch_bounds__(64) k_ising_scan(IsingScanArgs a) {
 // i's Q rows in registers.  The uniforms: numpy's stream generated on the device (words at woff[t] + 2 i:
 // k_mt_words, k_ising_scan), host-uploaded u [T][N], or null = Philox; mask: [T][ceil(N/32)] act_group bits
 // (null = all).
-template <int KMAX>
+//
+// kTrace (launch_ising_mfq_trace) adds, and the plain instantiations compile none of it: the clamp temperature of
+// the replica (temps[r]), the row of the per-stream inputs it reads (stream_of[r]), and per executed step
+// sum(reward) and the script's mse (:125-133) in a fixed summation order -- each lane its own agents in ascending
+// index, an xor butterfly (1, 2, .., 32) over the wave's 64 lanes, lane 0 the waves' partials in wave order, then
+// / (double)N.  No floating-point atomics: bitwise reproducible (include/magent_amd.h part 3b).
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+// reward_target of main_MFQ_Ising.py:77-81 for any K: (a ? 1 : -1) (2 s - K) / 2, exact in float64
+__device__ __forceinline__ double mfq_target(int st, int act, int K) {
+    return (double)((act ? 1 : -1) * (2 * st - K)) * 0.5;
+}
+
+template <int KMAX, bool kTrace = false>
 __global__ void __launch_bounds__(1024) k_ising_mfq(IsingMfqArgs a) {
     __shared__ uint8_t sp[4096];
     __shared__ int cnt[2];
+    __shared__ double wmse[kTrace ? 16 : 1];                          // the waves' partials (kTrace)
+    __shared__ int wrs[kTrace ? 16 : 1];
     const int r = blockIdx.x, N = a.N, K = a.K, i = threadIdx.x;
     const bool own = i < N;
+    int sr = r;                                                       // the row of the per-stream inputs
+    double temperature = a.temperature;
+    if constexpr (kTrace) {
+        if (a.stream_of) sr = a.stream_of[r];
+        if (a.temps) temperature = a.temps[r];
+    }
     double q[KMAX + 1][2];
 #pragma unroll
     for (int s = 0; s < KMAX + 1; ++s) { q[s][0] = 0.0; q[s][1] = 0.0; }
     int16_t nb[KMAX];
     for (int k = 0; k < K; ++k) nb[k] = own ? a.nbr[i * K + k] : 0;
-    if (own) sp[i] = a.spins0[(size_t)r * N + i];
+    if (own) sp[i] = a.spins0[(size_t)sr * N + i];
     if (i == 0) { cnt[0] = 0; cnt[1] = 0; }
     __syncthreads();
     double current_t = 0.3, max_order = 0.0;
@@ -304,7 +317,7 @@ __global__ void __launch_bounds__(1024) k_ising_mfq(IsingMfqArgs a) {
     const int words = (N + 31) >> 5;
     for (t = 0; t < a.T; ++t) {
         if (t % a.decay_gap == 0) current_t *= a.decay_rate;           // main_MFQ_Ising.py:108-112
-        if (current_t < a.temperature) current_t = a.temperature;
+        if (current_t < temperature) current_t = temperature;
         // ---- state = number of up neighbours (count_nonzero(obs == 1)), Boltzmann action (:55-67)
         int st = 0;
         int act = 0;
@@ -317,7 +330,7 @@ __global__ void __launch_bounds__(1024) k_ising_mfq(IsingMfqArgs a) {
             const double denom = e0 + e1;
             const double p0 = e0 / denom, p1 = e1 / denom;
             const double c0 = p0 / (p0 + p1);                          // cdf /= cdf[-1]
-            const double u = a.words ? mt_uniform(a.words + (size_t)r * a.wstride + a.woff[(size_t)r * (a.T + 1) + t] + 2 * i)
+            const double u = a.words ? mt_uniform(a.words + (size_t)sr * a.wstride + a.woff[(size_t)sr * (a.T + 1) + t] + 2 * i)
                            : a.u ? a.u[((size_t)r * a.T + t) * N + i]
                                  : philox_uniform(a.seed, (uint32_t)r, (uint32_t)t, (uint32_t)i);
             act = (u >= c0) ? 1 : 0;                                   // searchsorted(side='right')
@@ -328,20 +341,32 @@ __global__ void __launch_bounds__(1024) k_ising_mfq(IsingMfqArgs a) {
         __syncthreads();
         // ---- world.step: order parameter; reward on the new spins; Q update (:122-133)
         const int par = t & 1;
+        double term = 0.0;                                             // kTrace: this lane's mse term
+        int rsi = 0;                                                   // kTrace: this lane's reward, doubled
         if (own) {
             int sum = 0;
             for (int k = 0; k < K; ++k) sum += sp[nb[k]] ? 1 : -1;
             const double gi = act ? 1.0 : -1.0;
             const double rew = -((-0.5 * gi) * (double)sum);
-            const bool upd = !a.mask || ((a.mask[((size_t)r * a.T + t) * words + (i >> 5)] >> (i & 31)) & 1u);
+            const bool upd = !a.mask || ((a.mask[((size_t)sr * a.T + t) * words + (i >> 5)] >> (i & 31)) & 1u);
             if (upd) {
 #pragma unroll
                 for (int s = 0; s < KMAX + 1; ++s)
                     if (s == st) {
                         if (act) q[s][1] = q[s][1] + a.lr * (rew - q[s][1]);
                         else q[s][0] = q[s][0] + a.lr * (rew - q[s][0]);
+                        if constexpr (kTrace) {
+                            const double d = (act ? q[s][1] : q[s][0]) - mfq_target(st, act, K);
+                            term = d * d;
+                        }
                     }
             }
+            if constexpr (kTrace) rsi = act ? sum : -sum;              // reward = rsi / 2
+        }
+        if constexpr (kTrace) {
+            const double wm = wave_sum_f64(term);
+            const int wr = wave_sum_i32(rsi);
+            if ((i & 63) == 0) { wmse[i >> 6] = wm; wrs[i >> 6] = wr; }
         }
         const unsigned long long up = __ballot(own && act);
         if ((i & 63) == 0) atomicAdd(&cnt[par], __popcll(up));
@@ -351,6 +376,14 @@ __global__ void __launch_bounds__(1024) k_ising_mfq(IsingMfqArgs a) {
         if (i == 0) {
             if (a.order_out) a.order_out[(size_t)r * a.T + t] = order;
             if (a.nup_out) a.nup_out[(size_t)r * a.T + t] = n_up;
+            if constexpr (kTrace) {
+                const int nw = (int)blockDim.x >> 6;
+                double m = wmse[0];
+                int rs = wrs[0];
+                for (int w = 1; w < nw; ++w) { m = m + wmse[w]; rs += wrs[w]; }
+                if (a.mse_out) a.mse_out[(size_t)r * a.T + t] = m / (double)N;
+                if (a.rsum_out) a.rsum_out[(size_t)r * a.T + t] = (double)rs * 0.5;
+            }
         }
         if (order > max_order) max_order = order;                      // :138-156 (same on all lanes)
         if (fabs(max_order - order) < 0.001) ++done_;
@@ -373,17 +406,25 @@ __global__ void __launch_bounds__(1024) k_ising_mfq(IsingMfqArgs a) {
 // N > 1024 (up to kIsingMaxN): one 1024-lane workgroup per replica, lane l owns agents l, l + 1024, ...
 // The Q rows live in the output buffer (HBM, each row touched by its owner only) and the spins, the
 // new spins and the step's states in LDS (3 N bytes).  Same float64 operation sequence as k_ising_mfq.
-template <int KMAX>
+template <int KMAX, bool kTrace = false>
 __global__ void __launch_bounds__(1024) k_ising_mfq_big(IsingMfqArgs a) {
     extern __shared__ uint8_t lds[];
     __shared__ int cnt[2];
+    __shared__ double wmse[kTrace ? 16 : 1];                          // the waves' partials (kTrace)
+    __shared__ int wrs[kTrace ? 16 : 1];
     const int r = blockIdx.x, N = a.N, K = a.K;
+    int sr = r;                                                       // the row of the per-stream inputs
+    double temperature = a.temperature;
+    if constexpr (kTrace) {
+        if (a.stream_of) sr = a.stream_of[r];
+        if (a.temps) temperature = a.temps[r];
+    }
     uint8_t* sp = lds;                 // spins before the step
     uint8_t* nsp = lds + N;            // spins after the step (the actions)
     uint8_t* stl = lds + 2 * N;        // each agent's state (up-neighbour count) this step
     double* Q = a.q_out + (size_t)r * N * (K + 1) * 2;
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
-        sp[i] = a.spins0[(size_t)r * N + i];
+        sp[i] = a.spins0[(size_t)sr * N + i];
         for (int k = 0; k < 2 * (K + 1); ++k) Q[(size_t)i * (K + 1) * 2 + k] = 0.0;
     }
     if (threadIdx.x == 0) { cnt[0] = 0; cnt[1] = 0; }
@@ -393,7 +434,7 @@ __global__ void __launch_bounds__(1024) k_ising_mfq_big(IsingMfqArgs a) {
     const int words = (N + 31) >> 5;
     for (t = 0; t < a.T; ++t) {
         if (t % a.decay_gap == 0) current_t *= a.decay_rate;           // main_MFQ_Ising.py:108-112
-        if (current_t < a.temperature) current_t = a.temperature;
+        if (current_t < temperature) current_t = temperature;
         for (int i = threadIdx.x; i < N; i += blockDim.x) {            // state + Boltzmann action (:55-67)
             int st = 0;
             for (int k = 0; k < K; ++k) st += sp[a.nbr[i * K + k]];
@@ -403,7 +444,7 @@ __global__ void __launch_bounds__(1024) k_ising_mfq_big(IsingMfqArgs a) {
             const double denom = e0 + e1;
             const double p0 = e0 / denom, p1 = e1 / denom;
             const double c0 = p0 / (p0 + p1);
-            const double u = a.words ? mt_uniform(a.words + (size_t)r * a.wstride + a.woff[(size_t)r * (a.T + 1) + t] + 2 * i)
+            const double u = a.words ? mt_uniform(a.words + (size_t)sr * a.wstride + a.woff[(size_t)sr * (a.T + 1) + t] + 2 * i)
                            : a.u ? a.u[((size_t)r * a.T + t) * N + i]
                                  : philox_uniform(a.seed, (uint32_t)r, (uint32_t)t, (uint32_t)i);
             nsp[i] = (u >= c0) ? 1 : 0;
@@ -413,18 +454,31 @@ __global__ void __launch_bounds__(1024) k_ising_mfq_big(IsingMfqArgs a) {
         if (threadIdx.x == 0) cnt[par] = 0;
         __syncthreads();
         int ups = 0;
+        double macc = 0.0;                                             // kTrace: this lane's mse terms
+        int racc = 0;                                                  // kTrace: this lane's rewards, doubled
         for (int i = threadIdx.x; i < N; i += blockDim.x) {            // reward on the new spins, Q (:122-133)
             const int act = nsp[i];
             int sum = 0;
             for (int k = 0; k < K; ++k) sum += nsp[a.nbr[i * K + k]] ? 1 : -1;
             const double gi = act ? 1.0 : -1.0;
             const double rew = -((-0.5 * gi) * (double)sum);
-            const bool upd = !a.mask || ((a.mask[((size_t)r * a.T + t) * words + (i >> 5)] >> (i & 31)) & 1u);
+            const bool upd = !a.mask || ((a.mask[((size_t)sr * a.T + t) * words + (i >> 5)] >> (i & 31)) & 1u);
             if (upd) {
                 double* q = Q + ((size_t)i * (K + 1) + stl[i]) * 2 + act;
-                *q = *q + a.lr * (rew - *q);
+                const double qn = *q + a.lr * (rew - *q);
+                *q = qn;
+                if constexpr (kTrace) {
+                    const double d = qn - mfq_target(stl[i], act, K);
+                    macc = macc + d * d;
+                }
             }
+            if constexpr (kTrace) racc += act ? sum : -sum;
             ups += act;
+        }
+        if constexpr (kTrace) {
+            const double wm = wave_sum_f64(macc);
+            const int wr = wave_sum_i32(racc);
+            if ((threadIdx.x & 63) == 0) { wmse[threadIdx.x >> 6] = wm; wrs[threadIdx.x >> 6] = wr; }
         }
         atomicAdd(&cnt[par], ups);
         __syncthreads();
@@ -434,6 +488,13 @@ __global__ void __launch_bounds__(1024) k_ising_mfq_big(IsingMfqArgs a) {
         if (threadIdx.x == 0) {
             if (a.order_out) a.order_out[(size_t)r * a.T + t] = order;
             if (a.nup_out) a.nup_out[(size_t)r * a.T + t] = n_up;
+            if constexpr (kTrace) {
+                double m = wmse[0];
+                int rs = wrs[0];
+                for (int w = 1; w < 16; ++w) { m = m + wmse[w]; rs += wrs[w]; }
+                if (a.mse_out) a.mse_out[(size_t)r * a.T + t] = m / (double)N;
+                if (a.rsum_out) a.rsum_out[(size_t)r * a.T + t] = (double)rs * 0.5;
+            }
         }
         if (order > max_order) max_order = order;                      // :138-156 (same on all lanes)
         if (fabs(max_order - order) < 0.001) ++done_;
@@ -467,6 +528,22 @@ hipError_t launch_ising_mfq(const IsingMfqArgs& a, int R, hipStream_t st) {
         k_ising_mfq<4><<<R, threads, 0, st>>>(a);
     else
         k_ising_mfq<kIsingMaxK><<<R, threads, 0, st>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ising_mfq_trace(const IsingMfqArgs& a, int R, hipStream_t st) {
+    if (a.N > kIsingMaxN || a.K > kIsingMaxK) return hipErrorInvalidValue;
+    if (a.N > 1024) {
+        const size_t lds = 3 * (size_t)a.N;
+        if (a.K <= 4) k_ising_mfq_big<4, true><<<R, 1024, lds, st>>>(a);
+        else k_ising_mfq_big<kIsingMaxK, true><<<R, 1024, lds, st>>>(a);
+        return hipGetLastError();
+    }
+    const int threads = ((a.N + 63) / 64) * 64;
+    if (a.K <= 4)
+        k_ising_mfq<4, true><<<R, threads, 0, st>>>(a);
+    else
+        k_ising_mfq<kIsingMaxK, true><<<R, threads, 0, st>>>(a);
     return hipGetLastError();
 }
 
