@@ -271,6 +271,39 @@ int mfx_qnet_act_rollout(void *handle, const float *d_view, const float *d_feat,
                          int32_t *d_total, int32_t *d_act, void *stream);
 /* (the row count stays on the device: the kernels are launched for E * rowcap rows and read *d_total) */
 
+/* The opt-in Boltzmann acting mode of the Q network (csrc/qsample.h; tests/qsample_ref.py restates it).
+ * The reference's act, and every entry point above, is greedy; these draw the action instead.  For a row of f32 Q
+ * values q[0..A) -- exactly the values the forward writes to d_q -- and a temperature T:
+ *   weights   m = max_a q[a];  w[a] = expf((q[a] - m) / T), the subtraction and the IEEE division in f32, one
+ *             rounding each
+ *   draw      tot = the f32 sum of w in ascending action order;  thr = u * tot (one f32 multiply);  the action is
+ *             the first a whose running f32 sum, same order, satisfies run > thr, and A - 1 if none does (the rule
+ *             of the actor-critic draw)
+ *   uniform   u = the counter hash of (seed, step, group, row) that draws the actor-critic actions (ac_uniform):
+ *             row = i with group 0 for the forward, row = e * rowcap + j with the group index for a rollout, as
+ *             mfx_acnet_forward / mfx_acnet_act_rollout define it
+ *   non-finite rows   a row with any NaN or +-inf takes the greedy action (the first maximum over its non-NaN
+ *             entries; 0 if all are NaN), weights 1 there and 0 elsewhere: a rollout never gets an id made from NaNs
+ *   temperature   must be finite and > 0; anything else returns -1 (mfx_last_error) and nothing is launched
+ * Both follow the handle's precision and run on every rollout plan the greedy calls do; they change nothing but
+ * the action (and d_w): d_q is bit for bit mfx_qnet_forward's, and (d_act, d_w) are bit for bit mfx_q_sample's on
+ * that d_q.  The training target (mfx_mfq_target: max over e_q) is not part of this mode.  d_w: [n][A] weights out
+ * (null: not written); d_q, d_act may be null too. */
+int mfx_qnet_forward_sample(void *handle, const float *d_view, const float *d_feat, const float *d_prob, int n,
+                            float *d_q, float *d_w, int32_t *d_act, float temperature, uint32_t seed, uint32_t step,
+                            void *stream);
+int mfx_qnet_act_rollout_sample(void *handle, const float *d_view, const float *d_feat, const int32_t *d_counts,
+                                const double *d_mean, int mean_stride, int E, int G, int g, int rowcap, int32_t *d_rows,
+                                int32_t *d_total, int32_t *d_act, float temperature, uint32_t seed, uint32_t step,
+                                void *stream);
+/* The draw alone on a Q table in memory (k_q_sample): d_q [n][A] f32, 2 <= A <= 32 -> d_act [n], d_w [n][A] (either
+ * may be null); row i drawn with (seed, step, group, i) -- mfx_q_sample_rows: (seed, step, group, d_rows[i]), d_rows
+ * null: i. */
+int mfx_q_sample(const float *d_q, int n, int A, float temperature, uint32_t seed, uint32_t step, int group,
+                 float *d_w, int32_t *d_act, void *stream);
+int mfx_q_sample_rows(const float *d_q, const int32_t *d_rows, int n, int A, float temperature, uint32_t seed,
+                      uint32_t step, int group, float *d_w, int32_t *d_act, void *stream);
+
 /* The compact row list the act_rollout calls build: d_rows[i] = e * rowcap + j over envs e, j < min(counts[e][g],
  * rowcap), in env order; d_total[0] = the row count (d_total: 1 + ceil(E / 64) ints). */
 int mfx_rollout_rows(const int32_t *d_counts, int E, int G, int g, int rowcap, int32_t *d_rows, int32_t *d_total,

@@ -9,6 +9,8 @@
 //   (mean field) prob [A] --Prob-Emb 64, relu--> --Dense-Act-Prob 32, relu--> h_prob
 //   concat(h_obs, h_emb[, h_prob]) --Dense2 128, relu--> --Dense-Out 64, relu--> --Q-Value A--> q
 //   act = argmax q   (the reference takes argmax of softmax(q / T), the same index up to float ties)
+//   opt-in (k_qnet_head<.., true>, mfx_qnet_forward_sample / mfx_qnet_act_rollout_sample): act drawn from
+//   softmax(q / T) by the contract of qsample.h
 //
 // 3.4 MFLOP per agent (conv2 44 %, Dense-Obs 39 %, conv1 14 %): compute-bound at the f32 matrix rate
 // (157 TF/s -> ~4.6e7 agents/s for the whole chip).  Two kernels:
@@ -26,10 +28,12 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "mfx_common.h"
 #include "policy_gemm.h"
 #include "qnet_bf16.h"
+#include "qsample.h"
 #include "../../include/magent_amd.h"
 
 namespace mfx {
@@ -266,12 +270,13 @@ __global__ void __launch_bounds__(512, 1) k_qnet_conv2(QNetDev p, const float* _
 // register-staged wg_gemm_t.  LDS: the image path's 32 KB of chunks + the 12 KB ring, then the small layers'
 // wg_gemm_t staging from offset 0.
 constexpr size_t kQHeadImgSmem = kImgSmem + 3 * 1024 * 4 > kQHeadSmem ? kImgSmem + 3 * 1024 * 4 : kQHeadSmem;
-template <typename PT, bool kImg>
+// kSample: the Boltzmann draw of qsample.h in place of the argmax (qs; the greedy instantiations never read it).
+template <typename PT, bool kImg, bool kSample>
 __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __restrict__ conv, int n,
                                                       const float* __restrict__ feat, size_t feat_ld,
                                                       const PT* __restrict__ prob, size_t prob_ld, QRowMap rm,
                                                       float* __restrict__ q_out, int32_t* __restrict__ act_out,
-                                                      const int32_t* __restrict__ d_n, int n_off) {
+                                                      const int32_t* __restrict__ d_n, int n_off, QSample qs) {
     extern __shared__ __attribute__((aligned(16))) float qsm[];
     if (d_n) n = min(max(*d_n - n_off, 0), n);
     if ((int)blockIdx.x * kQHeadWaves * 16 >= n) return;          // (uniform: a launch sized for the upper bound)
@@ -369,14 +374,33 @@ __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __
             if (a < A) {
                 const float x = qv[t][r] + p.bq[a];
                 if (q_out && i < n) q_out[(size_t)i * A + a] = x;
-                if (x > best || (x == best && a < bi)) { best = x; bi = a; }
+                if constexpr (kSample) qv[t][r] = x;
+                else if (x > best || (x == best && a < bi)) { best = x; bi = a; }
             }
         }
+    if constexpr (kSample) {
+        // the agent's row gathered from its four lanes (every lane of the agent gets it; lane h == 0 uses it): the
+        // draw sums the weights in ascending action order
+        float x[kQSMaxA];
 #pragma unroll
-    for (int o = 16; o < 64; o <<= 1) {                  // lanes c, c + 16, c + 32, c + 48
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        for (int a = 0; a < kQSMaxA; ++a) x[a] = __shfl(qv[a >> 4][a & 3], 16 * ((a >> 2) & 3) + c);
+        if (h == 0 && i < n) {
+            // the uniform's row: the rollout row e * rowcap + j, or the row of the whole dense batch
+            bi = q_sample_row(x, A, qs.T, ac_uniform(qs.seed, qs.step, qs.group, rm.rows ? row : n_off + i));
+            if (qs.w) {
+                float* wr = qs.w + (size_t)i * A;
+#pragma unroll
+                for (int a = 0; a < kQSMaxA; ++a)
+                    if (a < A) wr[a] = x[a];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1) {              // lanes c, c + 16, c + 32, c + 48
+            const float ob = __shfl_xor(best, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
     }
     if (h == 0 && i < n && act_out) {
         const int r = rm.rows ? rm.rows[i] : i;
@@ -569,7 +593,7 @@ constexpr int kQPass = 1 << 18;
 // n rows (d_n: the count on the device, n its upper bound -- nothing is read back; launches sized for n).
 static int qnet_run(QNetHandle* q, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
                     const void* prob, int prob_f64, size_t prob_ld, QRowMap rm, int n, float* q_out, int32_t* act,
-                    hipStream_t st, const int32_t* d_n = nullptr) {
+                    hipStream_t st, const int32_t* d_n = nullptr, const QSample* qs = nullptr) {
     if (n <= 0) return 0;
     if (q->dev.use_mf && !prob) return fail("qnet: the mean-field net needs prob");
     const bool b16 = q->precision == 1;
@@ -591,9 +615,14 @@ static int qnet_run(QNetHandle* q, const float* view, size_t view_ld, const floa
                                            : (const void*)(static_cast<const float*>(prob) + (size_t)off * prob_ld);
         float* qo = q_out ? q_out + (size_t)off * q->dev.A : nullptr;
         int32_t* ao = act ? (r.rows ? act : act + off) : nullptr;
+        QSample s{};                                     // (sampling: this pass's rows of the weights)
+        if (qs) {
+            s = *qs;
+            if (s.w) s.w += (size_t)off * q->dev.A;
+        }
         if (b16) {
             MFX_HIP(qb16_forward(q->b16, v, view_ld, f, feat_ld, pb, prob_f64, prob_ld, r, m,
-                                 reinterpret_cast<uint16_t*>(q->conv.p), qo, ao, d_n, off, st));
+                                 reinterpret_cast<uint16_t*>(q->conv.p), qo, ao, d_n, off, st, qs ? &s : nullptr));
             continue;
         }
         const int cgrid = std::min((m + kQConv2Agents - 1) / kQConv2Agents, cus);
@@ -601,11 +630,13 @@ static int qnet_run(QNetHandle* q, const float* view, size_t view_ld, const floa
         MFX_HIP(hipGetLastError());
         const int hgrid = (m + 16 * kQHeadWaves - 1) / (16 * kQHeadWaves);
         const bool img = q->imaged;
-#define MFX_QHEAD(PT, IMG)                                                                                         \
-        k_qnet_head<PT, IMG><<<hgrid, 256, IMG ? kQHeadImgSmem : kQHeadSmem, st>>>(                                  \
-            q->dev, q->conv.p, m, f, feat_ld, static_cast<const PT*>(pb), prob_ld, r, qo, ao, d_n, off)
-        if (prob_f64) { if (img) MFX_QHEAD(double, true); else MFX_QHEAD(double, false); }
-        else { if (img) MFX_QHEAD(float, true); else MFX_QHEAD(float, false); }
+#define MFX_QHEAD(PT, IMG, SMP)                                                                                    \
+        k_qnet_head<PT, IMG, SMP><<<hgrid, 256, IMG ? kQHeadImgSmem : kQHeadSmem, st>>>(                             \
+            q->dev, q->conv.p, m, f, feat_ld, static_cast<const PT*>(pb), prob_ld, r, qo, ao, d_n, off, s)
+#define MFX_QHEAD_I(PT, SMP) do { if (img) MFX_QHEAD(PT, true, SMP); else MFX_QHEAD(PT, false, SMP); } while (0)
+        if (qs) { if (prob_f64) MFX_QHEAD_I(double, true); else MFX_QHEAD_I(float, true); }
+        else { if (prob_f64) MFX_QHEAD_I(double, false); else MFX_QHEAD_I(float, false); }
+#undef MFX_QHEAD_I
 #undef MFX_QHEAD
         MFX_HIP(hipGetLastError());
     }
@@ -643,6 +674,41 @@ MFX_API int mfx_qnet_act_rollout(void* handle, const float* d_view, const float*
     QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap};
     return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_mean + (size_t)g * mean_stride, 1, (size_t)G * mean_stride,
                     rm, E * rowcap, nullptr, d_act, st, d_total);
+}
+
+// The Boltzmann acting mode (qsample.h): refused before anything is launched unless T is finite and > 0.
+static int qsample_temperature(const char* who, float T) {
+    if (std::isfinite(T) && T > 0.f) return 0;
+    return fail("%s: the temperature must be finite and > 0; got %g", who, (double)T);
+}
+
+// mfx_qnet_forward with the action of row i drawn from the Boltzmann weights of its Q values at `temperature` with
+// the uniform (seed, step, group 0, row i); d_q are the values mfx_qnet_forward writes, d_w [n][A] the weights
+// (d_q, d_w, d_act: any may be null).
+MFX_API int mfx_qnet_forward_sample(void* handle, const float* d_view, const float* d_feat, const float* d_prob, int n,
+                                    float* d_q, float* d_w, int32_t* d_act, float temperature, uint32_t seed,
+                                    uint32_t step, void* stream) {
+    auto* q = static_cast<QNetHandle*>(handle);
+    MFX_CHECK(qsample_temperature("qnet_forward_sample", temperature));
+    QRowMap rm{nullptr, 1, 0, 0};
+    const QSample qs{temperature, seed, step, 0, d_w};
+    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_prob, 0, q->dev.A, rm, n, d_q, d_act, (hipStream_t)stream,
+                    nullptr, &qs);
+}
+
+// mfx_qnet_act_rollout with row j of env e drawn with the uniform (seed, step, g, e * rowcap + j).
+MFX_API int mfx_qnet_act_rollout_sample(void* handle, const float* d_view, const float* d_feat, const int32_t* d_counts,
+                                        const double* d_mean, int mean_stride, int E, int G, int g, int rowcap,
+                                        int32_t* d_rows, int32_t* d_total, int32_t* d_act, float temperature,
+                                        uint32_t seed, uint32_t step, void* stream) {
+    auto* q = static_cast<QNetHandle*>(handle);
+    MFX_CHECK(qsample_temperature("qnet_act_rollout_sample", temperature));
+    hipStream_t st = (hipStream_t)stream;
+    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
+    QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap};
+    const QSample qs{temperature, seed, step, g, nullptr};
+    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_mean + (size_t)g * mean_stride, 1, (size_t)G * mean_stride,
+                    rm, E * rowcap, nullptr, d_act, st, d_total, &qs);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "policy_gemm.h"
+#include "qsample.h"
 
 namespace mfx {
 
@@ -48,9 +49,10 @@ size_t qb16_total_units(int F, int use_mf);
 hipError_t qb16_build(QB16Net* net, const float* const* m, int F, int A, int use_mf, uint4* img, hipStream_t st);
 
 // One pass (m <= the pass size) of the forward: conv -> act (m x 2,592 bf16) -> head.  The arguments are those of
-// k_qnet_conv2 / k_qnet_head (policy_kernels.hip).
+// k_qnet_conv2 / k_qnet_head (policy_kernels.hip).  qs: the Boltzmann draw (qsample.h) in place of the argmax; null: greedy.
 hipError_t qb16_forward(const QB16Net& net, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
                         const void* prob, int prob_f64, size_t prob_ld, QRowMap rm, int m, uint16_t* act_buf,
-                        float* q_out, int32_t* act_out, const int32_t* d_n, int n_off, hipStream_t st);
+                        float* q_out, int32_t* act_out, const int32_t* d_n, int n_off, hipStream_t st,
+                        const QSample* qs = nullptr);
 
 }  // namespace mfx

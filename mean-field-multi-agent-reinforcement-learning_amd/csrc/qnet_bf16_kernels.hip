@@ -11,7 +11,8 @@
 //       - each layer's activation after bias and ReLU: Conv1 out, Conv2 out, h_obs, h_emb, Prob-Emb out, h_prob,
 //         Dense2 out, Dense-Out out.
 //   * Products are accumulated in f32 (the MFMA accumulator, which starts at the f32 bias); ReLU is applied in f32.
-//   * The Q values are written in f32, unrounded.  Argmax takes the first maximum.
+//   * The Q values are written in f32, unrounded.  Argmax takes the first maximum; the opt-in Boltzmann draw
+//     (k_qb16_head<.., true>) is qsample.h's, in f32 on those Q values.
 //   * An agent's result does not depend on its position in the batch or on the batch size: every agent is one
 //     column of its MFMAs, accumulated in one fixed order.
 //
@@ -226,11 +227,12 @@ __device__ __forceinline__ void layer_bias(f32x4 (&acc)[2][MT], const float* __r
     for (int t = 0; t < MT; ++t) acc[0][t] = acc[1][t] = bias4(bias, t, h);
 }
 
-template <typename PT>
+// kSample: the Boltzmann draw of qsample.h in place of the argmax (qs; the greedy instantiations never read it).
+template <typename PT, bool kSample>
 __global__ void __launch_bounds__(64 * kB16HeadWaves, 2)
 k_qb16_head(QB16Net p, const uint16_t* __restrict__ act, int n, const float* __restrict__ feat, size_t feat_ld,
             const PT* __restrict__ prob, size_t prob_ld, QRowMap rm, float* __restrict__ q_out,
-            int32_t* __restrict__ act_out, const int32_t* __restrict__ d_n, int n_off) {
+            int32_t* __restrict__ act_out, const int32_t* __restrict__ d_n, int n_off, QSample qs) {
     extern __shared__ __attribute__((aligned(16))) uint4 hsm[];
     if (d_n) n = min(max(*d_n - n_off, 0), n);
     if ((int)blockIdx.x * kB16HeadAgents >= n) return;            // (uniform: a launch sized for the upper bound)
@@ -375,11 +377,27 @@ k_qb16_head(QB16Net p, const uint16_t* __restrict__ act, int n, const float* __r
                     if (x > best || (x == best && u < bi)) { best = x; bi = u; }
                 }
             }
+        if constexpr (kSample) {
+            // the agent's row gathered from its four lanes (lane h == 0 uses it), as k_qnet_head does
+            float x[kQSMaxA];
 #pragma unroll
-        for (int o = 16; o < 64; o <<= 1) {              // lanes c, c + 16, c + 32, c + 48
-            const float ob = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bi, o);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+            for (int u = 0; u < kQSMaxA; ++u) x[u] = __shfl(qv[a][u >> 4][u & 3], 16 * ((u >> 2) & 3) + c);
+            if (h == 0 && i < n) {
+                bi = q_sample_row(x, A, qs.T, ac_uniform(qs.seed, qs.step, qs.group, rm.rows ? row[a] : n_off + i));
+                if (qs.w) {
+                    float* wr = qs.w + (size_t)i * A;
+#pragma unroll
+                    for (int u = 0; u < kQSMaxA; ++u)
+                        if (u < A) wr[u] = x[u];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int o = 16; o < 64; o <<= 1) {          // lanes c, c + 16, c + 32, c + 48
+                const float ob = __shfl_xor(best, o);
+                const int oi = __shfl_xor(bi, o);
+                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+            }
         }
         if (h == 0 && i < n && act_out) {
             const int r = rm.rows ? rm.rows[i] : i;
@@ -432,19 +450,21 @@ hipError_t qb16_build(QB16Net* net, const float* const* m, int F, int A, int use
 
 hipError_t qb16_forward(const QB16Net& net, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
                         const void* prob, int prob_f64, size_t prob_ld, QRowMap rm, int m, uint16_t* act_buf,
-                        float* q_out, int32_t* act_out, const int32_t* d_n, int n_off, hipStream_t st) {
+                        float* q_out, int32_t* act_out, const int32_t* d_n, int n_off, hipStream_t st,
+                        const QSample* qs) {
     if (m <= 0) return hipSuccess;
     const int cgrid = std::min((m + kB16ConvAgents - 1) / kB16ConvAgents, kB16ConvMaxGrid);
     k_qb16_conv<<<cgrid, 64 * kB16ConvAgents, kConvSmem, st>>>(net, view, view_ld, rm.rows, m, act_buf, d_n, n_off);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int hgrid = (m + kB16HeadAgents - 1) / kB16HeadAgents;
-    if (prob_f64)
-        k_qb16_head<double><<<hgrid, 64 * kB16HeadWaves, kHeadSmem, st>>>(
-            net, act_buf, m, feat, feat_ld, static_cast<const double*>(prob), prob_ld, rm, q_out, act_out, d_n, n_off);
-    else
-        k_qb16_head<float><<<hgrid, 64 * kB16HeadWaves, kHeadSmem, st>>>(
-            net, act_buf, m, feat, feat_ld, static_cast<const float*>(prob), prob_ld, rm, q_out, act_out, d_n, n_off);
+    const QSample s = qs ? *qs : QSample{};
+#define MFX_QB16_HEAD(PT, SMP)                                                                                      \
+    k_qb16_head<PT, SMP><<<hgrid, 64 * kB16HeadWaves, kHeadSmem, st>>>(                                              \
+        net, act_buf, m, feat, feat_ld, static_cast<const PT*>(prob), prob_ld, rm, q_out, act_out, d_n, n_off, s)
+    if (qs) { if (prob_f64) MFX_QB16_HEAD(double, true); else MFX_QB16_HEAD(float, true); }
+    else { if (prob_f64) MFX_QB16_HEAD(double, false); else MFX_QB16_HEAD(float, false); }
+#undef MFX_QB16_HEAD
     return hipGetLastError();
 }
 

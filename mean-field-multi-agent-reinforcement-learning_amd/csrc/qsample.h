@@ -1,0 +1,72 @@
+// qsample.h -- the Boltzmann draw over one row of Q values: the opt-in acting mode "boltzmann" of the Q network
+// (k_qnet_head, k_qb16_head with kSample) and the stand-alone k_q_sample (qsample_kernels.hip).  One function, three
+// users, so the three give the same action and the same weights bit for bit on the same Q row.
+//
+// CONTRACT (include/magent_amd.h; tests/qsample_ref.py restates it in numpy).  For a row q[0..A) of f32 Q
+// values -- exactly the values the forward writes to d_q -- and a temperature T (finite, > 0: the host refuses others):
+//   weights   m = max_a q[a];  w[a] = expf((q[a] - m) / T): an f32 subtraction and an f32 IEEE division, one rounding
+//             each (-ffp-contract=off), then expf
+//   draw      tot = the f32 sum of w in ascending action order;  thr = u * tot (one f32 multiply);  the action is the
+//             first a whose running f32 sum (same order) satisfies run > thr, and A - 1 if none does (k_acnet's rule)
+//   uniform   u = ac_uniform(seed, step, group, row) (acnet_bf16.h: the function the actor-critic draw uses)
+//   non-finite rows   a row with any NaN or +-inf entry takes the greedy action: the first maximum over its non-NaN
+//             entries (the greedy epilogue's rule), action 0 if every entry is NaN; its weights are 1 at that action
+//             and 0 elsewhere.  A rollout never receives an id the draw made from NaNs.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "acnet_bf16.h"
+
+namespace mfx {
+
+constexpr int kQSMaxA = 32;
+
+// The sampling arguments of the Q network's kernels (kSample instantiations; the greedy ones never read them).
+struct QSample {
+    float T;                        // temperature
+    uint32_t seed, step;
+    int group;
+    float* w;                       // [n][A] weights out, or null
+};
+
+// x[0..A): the row's Q values on entry (entries past A are not read), its weights on exit.  u: the row's uniform.
+__device__ __forceinline__ int q_sample_row(float (&x)[kQSMaxA], int A, float T, float u) {
+    float m = -__builtin_huge_valf();
+    int bi = -1;
+    bool finite = true;
+#pragma unroll
+    for (int a = 0; a < kQSMaxA; ++a)
+        if (a < A) {
+            finite = finite && __builtin_fabsf(x[a]) < __builtin_huge_valf();    // (false for NaN and +-inf)
+            if (x[a] > m || (x[a] == m && bi < 0)) { m = x[a]; bi = a; }        // first maximum, NaN never taken
+        }
+    if (!finite) {
+        bi = max(bi, 0);
+#pragma unroll
+        for (int a = 0; a < kQSMaxA; ++a)
+            if (a < A) x[a] = a == bi ? 1.f : 0.f;
+        return bi;
+    }
+    float tot = 0.f;
+#pragma unroll
+    for (int a = 0; a < kQSMaxA; ++a)
+        if (a < A) { x[a] = expf((x[a] - m) / T); tot += x[a]; }
+    const float thr = u * tot;
+    float run = 0.f;
+    int pick = -1;
+#pragma unroll
+    for (int a = 0; a < kQSMaxA; ++a)
+        if (a < A) {
+            run += x[a];
+            if (pick < 0 && run > thr) pick = a;
+        }
+    return pick < 0 ? A - 1 : pick;                      // (rounding: u * tot at the very top)
+}
+
+// n rows of a Q table [n][A] (2 <= A <= 32): act [n] and / or w [n][A]; row i drawn with (seed, step, group,
+// rows ? rows[i] : i).  One lane per row, grid-stride.
+hipError_t launch_q_sample(const float* q, const int32_t* rows, int n, int A, float T, uint32_t seed, uint32_t step,
+                           int group, float* w, int32_t* act, hipStream_t st);
+
+}  // namespace mfx

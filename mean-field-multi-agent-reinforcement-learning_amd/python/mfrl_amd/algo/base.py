@@ -5,6 +5,8 @@ Inputs may be numpy arrays (the reference's call sites) or device tensors (the b
 outputs follow the reference: act -> int32 numpy, calc_target_q -> float64, train -> (loss, stats).
 """
 import copy
+import math
+import zlib
 
 import numpy as np
 import torch
@@ -26,10 +28,22 @@ def weights_key(net, gen=0):
     return (gen, tuple((p.data_ptr(), p._version) for p in net.parameters()))
 
 
+EXPLORE = ("greedy", "boltzmann")       # ValueNet.explore
+
+
+def check_temperature(t):
+    """The Boltzmann temperature as a float; ValueError unless it is finite and > 0 (the library refuses it too)."""
+    t = float(t)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError("explore 'boltzmann': the temperature (eps) must be finite and > 0, got %r" % (t,))
+    return t
+
+
 class ValueNet:
-    graph_train = True          # train() replays the minibatch step as a HIP graph (train_batches)
+    graph_train = True         # train() replays the minibatch step as a HIP graph (train_batches)
     act_precision = "f32"       # act_dev's HIP forward: "f32", or "bf16" operands (mfrl_amd.policy); training stays f32
     _train_backend = "torch"    # train_batches: "torch" (the graph below), or "hip" (mfrl_amd.qtrain, csrc/qtrain_kernels.hip)
+    _explore = "greedy"         # act_dev / act_rollout: "greedy" (the reference's argmax), or "boltzmann" (csrc/qsample.h)
 
     def __init__(self, sess, env, handle, name, update_every=5, use_mf=False, learning_rate=1e-4, tau=0.005,
                  gamma=0.95):
@@ -57,6 +71,25 @@ class ValueNet:
         self._graph = None
         self._wgen = 0              # bumped after graph replays (they update the weights behind torch's back)
         self._hip_key = None
+        self._draws = 0             # acting calls: the step counter of the Boltzmann draw (explore = "boltzmann")
+        # the draw's seed, made as ActorCritic makes its own: the run's torch seed mixed with the model name; np.random
+        # is left alone (the replay buffers consume it, and seeded runs must sample the same indices)
+        self.seed = zlib.crc32(("%s/%s/%d" % ("mfq" if use_mf else "dqn", name, torch.initial_seed())).encode())
+
+    @property
+    def explore(self):
+        """How act_dev / act_rollout choose: "greedy" (the default and the reference's act: argmax q; eps is only
+        stored) or "boltzmann" (opt-in): the action is drawn from softmax(q / T) with T = the call's eps, by the
+        contract of csrc/qsample.h -- the uniform of a row is the counter hash of (self.seed, the count of acting
+        calls, the group, the row), so np.random is not consumed and seeded runs repeat.  Training is the same in both
+        modes (the target stays the reference's max rule)."""
+        return self._explore
+
+    @explore.setter
+    def explore(self, value):
+        if value not in EXPLORE:
+            raise ValueError("explore %r (one of %s)" % (value, ", ".join(EXPLORE)))
+        self._explore = value
 
     @property
     def train_backend(self):
@@ -232,12 +265,23 @@ class ValueNet:
         """Device in, device out: int32 greedy actions (algo/base.py:228-254).  The Battle view runs the
         hand-written HIP forward (mfrl_amd.policy.QNetHIP, csrc/policy_kernels.hip; act_precision = "bf16":
         csrc/qnet_bf16_kernels.hip) with the eval net's current weights: argmax of e_q, the reference's argmax softmax(e_q / temperature) up to float ties.
-        Other view shapes (not in the shipped configs) run the torch module."""
+        Other view shapes (not in the shipped configs) run the torch module.
+
+        explore = "boltzmann" (opt-in): row i is drawn from softmax(e_q / eps) instead, with the uniform (self.seed,
+        the count of acting calls, group 0, row i) -- fused into the HIP forward's epilogue for the Battle view,
+        mfrl_amd.mf.q_sample on the torch module's Q values otherwise (2..32 actions).  eps must be finite and > 0."""
         view, feat = as_dev(kwargs["state"][0]), as_dev(kwargs["state"][1])
         self.temperature = kwargs["eps"]
         prob = self._prob(kwargs, len(view))
         if self.use_mf:
             assert len(prob) == len(view)
+        if self._explore == "boltzmann":
+            T = check_temperature(self.temperature)
+            self._draws += 1
+            if self.view_space == (13, 13, 7) and self.num_actions <= 32:
+                return self._hip_current().act(view, feat, prob, temperature=T, seed=self.seed, step=self._draws)
+            e_q = self.eval_net(view, feat, prob).float().contiguous()
+            return mf.q_sample(e_q, T, self.seed, self._draws)
         if self.view_space == (13, 13, 7) and self.num_actions <= 32:
             return self._hip_current().act(view, feat, prob)
         e_q = self.eval_net(view, feat, prob)
@@ -258,17 +302,28 @@ class ValueNet:
         return self._hip
 
     @torch.no_grad()
-    def act_rollout(self, eng, group):
+    def act_rollout(self, eng, group, eps=None):
         """Greedy actions of group `group` of a BattleBatch's rollout from its observation buffers into its action
         buffer (mfrl_amd.policy.QNetHIP.act_rollout), with the eval net's current weights; nothing is read back.
         The weights are uploaded on the caller's current stream: when they moved and the engine sits on another
-        stream, the engine's stream waits for the upload."""
+        stream, the engine's stream waits for the upload.
+
+        explore = "boltzmann": row j of env e is drawn from softmax(q / eps) with the uniform (self.seed, the count
+        of acting calls, group, e * rowcap + j); eps None: self.temperature (the last eps, 0.1 at first).  With the
+        default "greedy", eps is not used."""
         if not (self.view_space == (13, 13, 7) and self.num_actions <= 32):
             raise ValueError("act_rollout: the HIP forward takes the Battle view (13, 13, 7) and at most 32 actions")
         before = self._hip_key
         hip = self._hip_current()
         if self._hip_key != before and eng.stream_handle() != torch.cuda.current_stream().cuda_stream:
             eng.torch_stream().wait_stream(torch.cuda.current_stream())
+        if self._explore == "boltzmann":
+            if eps is not None:
+                self.temperature = eps
+            T = check_temperature(self.temperature)
+            self._draws += 1
+            hip.act_rollout(eng, group, temperature=T, seed=self.seed, step=self._draws)
+            return
         hip.act_rollout(eng, group)
 
     def act(self, **kwargs):

@@ -211,7 +211,8 @@ def play_rollout(eng, n_round, map_size, max_steps, models, print_every=50, eps=
 
     Unlike play_batched, which idles an env once it is done, an env that ends early (done, or max_steps steps into
     its episode) restarts inside the loop from the same placement and keeps producing rows: every round is exactly
-    max_steps steps of every env.  The greedy policy does not use eps (as in play_batched).
+    max_steps steps of every env.  The greedy policy does not use eps (as in play_batched); a model with
+    explore = "boltzmann" samples at temperature eps (ValueNet.act_rollout).
 
     Returns (max_nums, nums, mean_rewards, total_rewards) summed over envs like play_batched, computed once at the
     end from the rollout's stats, episode_return and group_num buffers: total_rewards[g] is the return of every
@@ -261,6 +262,15 @@ def play_rollout_episodes(eng, n_round, map_size, max_steps, models, print_every
                           lambda: models[0].rollout_collector(eng, 0), models[0].train_rollout, recorder)
 
 
+def _act_rollout(model, eng, g, eps):
+    """model.act_rollout for one group of a device-loop round: a model that explores (ValueNet.explore other than
+    "greedy") gets the round's eps as its temperature; every other model is called as it always was."""
+    if getattr(model, "explore", "greedy") != "greedy":
+        model.act_rollout(eng, g, eps=eps)
+    else:
+        model.act_rollout(eng, g)
+
+
 def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, left_id, collector, train_fn,
                    recorder=None):
     """The round of play_rollout / play_rollout_episodes: collector() gives group 0's RolloutCollector, train_fn()
@@ -284,7 +294,7 @@ def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, 
     t_play = time.time()
     for step_ct in range(max_steps):
         for g in range(G):
-            models[g].act_rollout(eng, g)
+            _act_rollout(models[g], eng, g, eps)
         if col is not None:
             col.begin()
         eng.rollout_policy_step()
@@ -329,8 +339,9 @@ def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, ep
     Only each env's first episode counts: every env finishes it within max_steps steps (the rollout's episode cap), so
     a round is exactly E episodes, as E rounds of battle() are; counting every episode that ends inside a fixed window
     would over-weight the short ones.  The round stops at max_steps steps, or at the first multiple of check_every
-    steps at which every env has finished its first episode.  eps is not used (act_rollout is greedy for the Q
-    models and samples for the actor-critic ones, as battle() with eps 0 does).  board: a RolloutScoreboard of `eng`
+    steps at which every env has finished its first episode.  eps is the temperature of the Q models whose explore is
+    "boltzmann" (it must then be finite and > 0) and is not used otherwise: act_rollout is greedy for the Q models by
+    default and samples for the actor-critic ones, as battle() with eps 0 does.  board: a RolloutScoreboard of `eng`
     with target 1 and ep_cap >= 1 to keep score on, so that its buffers are reused from round to round (battle_eval
     passes one); None: one is made for this round.  recorder: a mfrl_amd.recorder.RolloutRecorder of `eng` that records
     its watched envs over the round (one more launch per step); the outcome then holds the round's "trace".
@@ -369,7 +380,7 @@ def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, ep
     step_ct = 0
     while step_ct < max_steps:
         for g in range(G):
-            models[g].act_rollout(eng, g)
+            _act_rollout(models[g], eng, g, eps)
         eng.rollout_policy_step()
         board.update()
         if recorder is not None:

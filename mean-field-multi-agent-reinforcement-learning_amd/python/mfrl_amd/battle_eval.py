@@ -5,6 +5,7 @@ algorithms, play --n_round evaluation rounds; the last line is the reference's W
     python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --idx 1999 1999     # the device rollout loop
     python -m mfrl_amd.battle_eval --algo mfac --oppo ac --envs 8192 --act_precision bf16 --idx 1999 1999
     python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --watch 0 63 --idx 1999 1999    # + frames of two envs
+    python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --explore boltzmann --temperature 0.1 --idx 1999 1999
 
 Models are loaded from <base_dir>/data/models/<algo>-0 and <base_dir>/data/models/<oppo>-1 at the two --idx steps, as
 the reference does (train_battle saves them there).  --envs 1 is the reference's path unchanged: tools.Runner with
@@ -16,6 +17,7 @@ records those envs of the first --watch_rounds rounds on the device (mfrl_amd.re
 on the one-env engine and writes the reference's frame files under <render dir>/round_<k>/env_<e>/.
 """
 import argparse
+import math
 import os
 import time
 
@@ -49,9 +51,23 @@ def main(argv=None):
                         help="with --envs > 1: record these envs (at most 16) on the device rollout loop and write the "
                              "frames of their first episode")
     parser.add_argument("--watch_rounds", type=int, default=1, help="rounds --watch records (the first ones)")
+    parser.add_argument("--explore", type=str, choices=["greedy", "boltzmann"], default="greedy",
+                        help="how the Q models (mfq / il) of the pairing act: greedy (the reference: argmax q) or boltzmann "
+                             "(drawn from softmax(q / --temperature))")
+    parser.add_argument("--temperature", type=float, default=None,
+                        help="with --explore boltzmann: the temperature, finite and > 0 (default 0.1)")
     args = parser.parse_args(argv)
     if args.oppo is None:
         args.oppo = args.algo
+    if args.explore != "greedy" and args.algo not in ("mfq", "il") and args.oppo not in ("mfq", "il"):
+        parser.error("--explore boltzmann samples from the Q values: neither --algo nor --oppo is mfq or il")
+    if args.temperature is not None and args.explore == "greedy":
+        parser.error("--temperature is the Boltzmann temperature: give --explore boltzmann too")
+    if args.explore != "greedy":
+        args.temperature = 0.1 if args.temperature is None else args.temperature
+        if not (math.isfinite(args.temperature) and args.temperature > 0):
+            parser.error("--temperature must be finite and > 0")
+    eps = args.temperature if args.explore != "greedy" else 0.0      # (greedy: the reference's battle() eps)
     if args.n_round < 1:
         parser.error("--n_round must be at least 1")
     if args.envs < 1:
@@ -95,13 +111,16 @@ def main(argv=None):
     if not args.untrained:
         models[0].load(main_model_dir, step=args.idx[0])
         models[1].load(oppo_model_dir, step=args.idx[1])
+    for m in models:
+        if args.explore != "greedy" and hasattr(type(m), "explore"):     # (the Q models of the pairing)
+            m.explore = args.explore
     win_cnt = {"main": 0, "opponent": 0}
     t0 = time.time()
     if args.envs == 1:
         # (battle.py:62 passes render_every=0 whatever --render says; so does this)
         runner = tools.Runner(None, env, handles, args.map_size, args.max_steps, models, battle, render_every=0)
         for k in range(args.n_round):
-            runner.run(0.0, k, win_cnt=win_cnt)
+            runner.run(eps, k, win_cnt=win_cnt)
         episodes = args.n_round
     else:
         from .battle import BattleBatch
@@ -118,7 +137,7 @@ def main(argv=None):
         steps = 0
         for k in range(args.n_round):
             watching = rec is not None and k < args.watch_rounds
-            out = battle_rollout(eng, k, args.map_size, args.max_steps, models, eps=0.0, board=board,
+            out = battle_rollout(eng, k, args.map_size, args.max_steps, models, eps=eps, board=board,
                                  recorder=rec if watching else None)[4]
             if watching:         # behind the round: nothing of the one-env engine runs beside the rollout loop
                 for j, e in enumerate(args.watch):

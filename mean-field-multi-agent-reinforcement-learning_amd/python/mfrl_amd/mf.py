@@ -4,6 +4,8 @@
     mfq_target(e_q, t_q, rewards, dones, g)  algo/base.py:192-220 (ValueNet.calc_target_q), float64
     mfac_returns(rewards, offsets, values, g) algo/ac.py:305-320 (discounted returns, float64 running
                                              return stored as float32: the reference's NumPy-1 rules)
+    q_sample(q, temperature, seed, step)     the Boltzmann draw over Q rows (csrc/qsample.h): the opt-in exploration
+                                             of the Q models; no counterpart in the reference, whose act is greedy
 """
 import ctypes
 
@@ -59,6 +61,30 @@ def mfq_target(e_q, t_q, rewards, dones, gamma=0.95):
     check(L.mfx_mfq_target(_p(e_q.contiguous()), _p(t_q.contiguous()), _p(rewards.contiguous()), _p(d), M, A,
                            ctypes.c_double(gamma), _p(out), _stream()), "mfx_mfq_target")
     return out
+
+
+def q_sample(q, temperature, seed, step, group=0, rows=None, want_w=False):
+    """The Boltzmann draw of the Q models' opt-in acting mode on a Q table (k_q_sample; the contract of csrc/qsample.h,
+    restated in tests/qsample_ref.py): q float32 [n, A], 2 <= A <= 32 -> actions int32 [n], row i drawn from the
+    weights expf((q - max q) / temperature) with the uniform (seed, step, group, rows[i] if rows is given else i); a
+    row with a non-finite entry takes its greedy action.  rows: int32 [n] (e.g. e * rowcap + j of a rollout).
+    want_w: (actions, weights float32 [n, A]).  A temperature that is not finite and > 0 raises; nothing is launched."""
+    _dtype("q_sample", q=(q, torch.float32))
+    if rows is not None:
+        _dtype("q_sample", rows=(rows, torch.int32))
+        if rows.shape != (q.shape[0],):
+            raise ValueError("q_sample: rows of shape %s for %d table rows" % (tuple(rows.shape), q.shape[0]))
+        rows = rows.contiguous()
+    n, A = q.shape
+    act = torch.empty(n, dtype=torch.int32, device=q.device)
+    w = torch.empty((n, A), dtype=torch.float32, device=q.device) if want_w else None
+    L = lib()
+    L.mfx_q_sample_rows.restype = ctypes.c_int
+    null = ctypes.c_void_p()
+    check(L.mfx_q_sample_rows(_p(q.contiguous()), _p(rows) if rows is not None else null, n, A, ctypes.c_float(temperature),
+                              ctypes.c_uint32(seed & 0xFFFFFFFF), ctypes.c_uint32(step & 0xFFFFFFFF), int(group),
+                              _p(w) if want_w else null, _p(act), _stream()), "mfx_q_sample")
+    return (act, w) if want_w else act
 
 
 def mfac_returns(rewards, offsets, values, gamma=0.95, numpy1=True):

@@ -21,6 +21,11 @@ the quantisation error (a few 1e-3 of the Q scale, tests/test_policy_bf16_cpu.py
 differ where the top two Q values are that close.  The contract is stated in csrc/qnet_bf16_kernels.hip and
 restated in numpy in tests/qnet_bf16_ref.py.
 
+temperature=T on forward / act / act_rollout (opt-in; None, the default, is the reference's greedy act): the action is
+drawn from softmax(q / T) in the same kernels' epilogue, in both precisions -- the contract of csrc/qsample.h (f32
+weights expf((q - max q) / T), a running-sum draw against the actor-critic draw's counter-hash uniform), restated in
+numpy in tests/qsample_ref.py.  The Q values are the greedy call's bit for bit.
+
 ACNetHIP: the actor-critic network (ActorCritic / MFAC, algo/ac.py) on csrc/acnet_kernels.hip, the same two modes.
 precision="bf16" is the policy path only -- view, feature, dense 512, x / 0.1, policy, the draw -- on
 csrc/acnet_bf16_kernels.hip: the four weight matrices, the view and feature inputs, h_view and h_emb after bias and
@@ -161,6 +166,9 @@ class QNetHIP:
         for fn in ("mfx_qnet_create", "mfx_qnet_destroy", "mfx_qnet_set_weights", "mfx_qnet_forward",
                    "mfx_qnet_act_rollout", "mfx_qnet_set_precision", "mfx_qnet_precision"):
             getattr(L, fn).restype = ctypes.c_int
+        for fn in ("mfx_qnet_forward_sample", "mfx_qnet_act_rollout_sample"):    # (absent from older builds, which
+            if hasattr(L, fn):                                                   #  the bench scripts may load)
+                getattr(L, fn).restype = ctypes.c_int
         self._L = L
         self.blob_n, self.offsets = blob_layout(self.F, self.A, self.use_mf)
         hdl = _P()
@@ -187,9 +195,16 @@ class QNetHIP:
         return self
 
     # ------------------------------------------------------------------ forward
-    def forward(self, view, feature, prob=None, want_q=True):
+    def forward(self, view, feature, prob=None, want_q=True, temperature=None, seed=0, step=0, want_w=False):
         """view [n, 13, 13, 7], feature [n, F], prob [n, A] (mean field) float32 CUDA tensors ->
-        (q [n, A] float32 or None, actions [n] int32 = argmax q)."""
+        (q [n, A] float32 or None, actions [n] int32 = argmax q).
+
+        temperature (the opt-in Boltzmann mode; None: greedy, the call above): row i's action is drawn from the weights
+        expf((q - max q) / temperature) with the uniform (seed, step, group 0, row i) -- the contract of csrc/qsample.h,
+        restated in tests/qsample_ref.py; q is what the greedy call gives.  want_w: the weights [n, A] float32 as a
+        third result.  A temperature that is not finite and > 0 raises (nothing is launched)."""
+        if temperature is None and want_w:
+            raise ValueError("QNetHIP.forward: want_w needs a temperature")
         n = view.shape[0]
         view = view.reshape(n, -1).contiguous().float()
         feature = feature.reshape(n, -1).contiguous().float()
@@ -198,16 +213,26 @@ class QNetHIP:
             prob = prob.reshape(n, -1).contiguous().float()
         q = torch.empty((n, self.A), dtype=torch.float32, device=view.device) if want_q else None
         act = torch.empty(n, dtype=torch.int32, device=view.device)
+        if temperature is not None:
+            w = torch.empty((n, self.A), dtype=torch.float32, device=view.device) if want_w else None
+            check(self._L.mfx_qnet_forward_sample(self.handle, _ptr(view), _ptr(feature),
+                                                  _ptr(prob if self.use_mf else None), int(n), _ptr(q), _ptr(w), _ptr(act),
+                                                  ctypes.c_float(temperature), ctypes.c_uint32(seed & 0xFFFFFFFF),
+                                                  ctypes.c_uint32(step & 0xFFFFFFFF), _stream()),
+                  "mfx_qnet_forward_sample")
+            return (q, act, w) if want_w else (q, act)
         check(self._L.mfx_qnet_forward(self.handle, _ptr(view), _ptr(feature), _ptr(prob if self.use_mf else None),
                                        int(n), _ptr(q), _ptr(act), _stream()), "mfx_qnet_forward")
         return q, act
 
-    def act(self, view, feature, prob=None):
-        return self.forward(view, feature, prob, want_q=False)[1]
+    def act(self, view, feature, prob=None, temperature=None, seed=0, step=0):
+        return self.forward(view, feature, prob, want_q=False, temperature=temperature, seed=seed, step=step)[1]
 
-    def act_rollout(self, eng, group):
+    def act_rollout(self, eng, group, temperature=None, seed=0, step=0):
         """Actions of group `group` of a BattleBatch rollout from its current observation buffers and
         former mean actions, written into the rollout's action buffer [E][G][rowcap] (live rows only).
+        temperature (None: greedy): the Boltzmann draw of forward(), row j of env e with the uniform
+        (seed, step, group, e * rowcap + j).
 
         Works on every plan that takes a learned policy (BattleBatch.rollout_policy_path: all but
         MFX_ROLLOUT_PIPE=1 -- large batches, large envs and few-env batches alike; E, rowcap and the buffers come
@@ -223,6 +248,13 @@ class QNetHIP:
                                                           else 0, ctypes.byref(p), ctypes.byref(nb)), "rollout_buffer")
             ptr[name] = p
         stride = eng.mean_stride()
+        if temperature is not None:
+            check(self._L.mfx_qnet_act_rollout_sample(
+                self.handle, ptr["view"], ptr["feature"], ptr["group_num"], ptr["mean_action"], int(stride), int(E),
+                int(G), int(group), int(rc), _P(self._rows.data_ptr()), _P(self._rows.data_ptr() + 4 * E * rc),
+                ptr["actions"], ctypes.c_float(temperature), ctypes.c_uint32(seed & 0xFFFFFFFF),
+                ctypes.c_uint32(step & 0xFFFFFFFF), _P(eng.stream_handle())), "mfx_qnet_act_rollout_sample")
+            return
         check(self._L.mfx_qnet_act_rollout(self.handle, ptr["view"], ptr["feature"], ptr["group_num"],
                                            ptr["mean_action"], int(stride), int(E), int(G), int(group), int(rc),
                                            _P(self._rows.data_ptr()), _P(self._rows.data_ptr() + 4 * E * rc),

@@ -7,6 +7,7 @@
     python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes ...   # the device rollout loop (ac / mfac)
     python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes --ac_train_backend hip ...   # + the HIP step
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --render --watch 0 63 ...   # + frames of two envs
+    python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann ...   # sample from softmax(q / eps)
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -67,7 +68,13 @@ def main(argv=None):
     parser.add_argument("--watch", type=int, nargs="+", metavar="ENV",
                         help="with --rollout / --rollout_episodes: record these envs (at most 16) on the rounds --render "
                              "marks and write their frames (mfrl_amd.recorder)")
+    parser.add_argument("--explore", type=str, choices=["greedy", "boltzmann"], default="greedy",
+                        help="mfq / il: how the models act while they play -- greedy (the reference: argmax q, the eps "
+                             "schedule unused) or boltzmann (drawn from softmax(q / eps), eps from the schedule)")
     args = parser.parse_args(argv)
+    if args.explore != "greedy" and args.algo not in ("mfq", "il"):
+        parser.error("--explore boltzmann samples from the Q values: --algo mfq or il (ac / mfac sample from their "
+                     "policy already)")
     if args.ac_train_backend == "hip" and args.algo not in ("ac", "mfac"):
         parser.error("--ac_train_backend hip trains the actor-critic network: --algo ac or mfac (mfq / il: "
                      "--train_backend hip)")
@@ -116,6 +123,8 @@ def main(argv=None):
             m.train_backend = args.ac_train_backend
         if args.act_precision != "f32":
             m.act_precision = args.act_precision
+        if args.explore != "greedy":
+            m.explore = args.explore
     play_handle = play
     if args.envs > 1:
         from .battle import BattleBatch
