@@ -239,6 +239,26 @@ int mfx_mean_action(const int32_t *d_acts, const int32_t *d_counts, int B, int r
 /* algo/base.py:192-220 */
 int mfx_mfq_target(const float *d_eq, const float *d_tq, const float *d_r, const uint8_t *d_done, int M, int A,
                    double gamma, double *d_out, void *stream);
+/* The opt-in Boltzmann mean-field value target (csrc/qsample.h; tests/qtarget_ref.py restates it): the
+ * paper's v^MF (arXiv 1802.05438 eqs. 9-11), the value of the next state under the policy that acts, where
+ * mfx_mfq_target takes the value of the greedy action.  It has no counterpart in the reference.  For one row, with
+ * e_q[0..A) from the eval net and t_q[0..A) from the target net on the next state, 2 <= A <= 32, temperature T:
+ *   weights   exactly the acting weights of mfx_q_sample at T: m = max e_q, w[a] = expf((e_q[a] - m) / T) in f32, one
+ *             rounding per operation -- its non-finite rule included: a row of e_q with any NaN or +-inf has w = 1 at
+ *             its greedy action (first maximum over the non-NaN entries, 0 if all are NaN) and 0 elsewhere.  (The max
+ *             rule's argmax lets the first NaN win; this rule follows the acting policy instead.)
+ *   value     num = sum_a f64(w[a]) f64(t_q[a]), den = sum_a f64(w[a]), both in ascending action order in float64
+ *             (each product is exact there); v = num / den, one f64 division.  A NaN or infinite t_q[a] makes v NaN
+ *             even where w[a] = 0.
+ *   target    y = f64(r) + ((1 - done) * v) * gamma: the form, the dtype rules and the `done` reading (any non-zero
+ *             byte) of mfx_mfq_target; float64 out.
+ * One lane per row (k_mfq_target_soft).  d_T, when not null, is a one-element f32 device value that overrides T (a
+ * captured graph follows a temperature that changes between replays); a device-side temperature that is not finite
+ * and > 0 makes every target (and d_w entry) of that launch NaN.  A outside 2..32, and with d_T null a T that is not
+ * finite and > 0, return -1 (mfx_last_error) and nothing is launched.  M = 0 is a no-op.  d_w: [M][A] weights out,
+ * or null. */
+int mfx_mfq_target_boltzmann(const float *d_eq, const float *d_tq, const float *d_r, const uint8_t *d_done, int M, int A,
+                             double gamma, float T, const float *d_T, double *d_out, float *d_w, void *stream);
 /* algo/ac.py:305-320 -- numpy1 = 1: the reference's NumPy-1 promotion (float64 running return, the
  * default of the python wrapper); 0: NEP-50 (float32), as the same lines run under NumPy 2 */
 int mfx_mfac_returns(float *d_rew, const int64_t *d_offsets, const float *d_value, int n_ep, double gamma,
@@ -287,7 +307,8 @@ int mfx_qnet_act_rollout(void *handle, const float *d_view, const float *d_feat,
  *   temperature   must be finite and > 0; anything else returns -1 (mfx_last_error) and nothing is launched
  * Both follow the handle's precision and run on every rollout plan the greedy calls do; they change nothing but
  * the action (and d_w): d_q is bit for bit mfx_qnet_forward's, and (d_act, d_w) are bit for bit mfx_q_sample's on
- * that d_q.  The training target (mfx_mfq_target: max over e_q) is not part of this mode.  d_w: [n][A] weights out
+ * that d_q.  The training target is not part of this mode (mfx_mfq_target: max over e_q, unless the opt-in
+ * mfx_mfq_target_boltzmann / mfx_qtrain_set_target is chosen as well).  d_w: [n][A] weights out
  * (null: not written); d_q, d_act may be null too. */
 int mfx_qnet_forward_sample(void *handle, const float *d_view, const float *d_feat, const float *d_prob, int n,
                             float *d_q, float *d_w, int32_t *d_act, float temperature, uint32_t seed, uint32_t step,
@@ -578,6 +599,13 @@ int mfx_trace_update(const mfx_trace_src *src, const mfx_trace_dst *dst, int64_t
  * mfx_qnet_set_weights device to device.
  *   set_hyper        defaults: lr 1e-4, betas 0.9 / 0.999, eps 1e-8 (torch's Adam), tau 0.005, gamma 0.95; eps must be
  *                    > 0 (an entry whose g, m and v are all zero divides by it and must stay zero)
+ *   set_target       the rule of y (host state, read by the grads / run calls that follow): MFX_QTARGET_MAX, the
+ *                    default and the reference's rule above, or MFX_QTARGET_BOLTZMANN (opt-in): y = f32(f64(r)
+ *                    + ((1 - done) v) gamma) with v of mfx_mfq_target_boltzmann -- weights from q_eval on the next rows
+ *                    at `temperature`, values from q_target on the next rows -- rounded once to f32.  The temperature
+ *                    must be finite and > 0 (read only for the boltzmann rule) and the handle have >= 2 actions; a
+ *                    refusal leaves the handle as it was.  Launch count, buffers and bitwise reproducibility are
+ *                    the same under both rules, and MAX after BOLTZMANN is bit for bit a fresh handle's MAX.
  *   set/get_state    `which` = MFX_QTRAIN_EVAL / TARGET / ADAM_M / ADAM_V; n_floats must be the blob size; a copy on
  *                    `stream`.  Setting eval or target leaves the moments and the step count alone.
  *   reset_optimizer  zeroes m, v and the step count
@@ -604,9 +632,11 @@ typedef struct mfx_qtrain_ring {          /* MemoryGroup's ring columns, rows [0
 } mfx_qtrain_ring;
 enum { MFX_QTRAIN_EVAL = 0, MFX_QTRAIN_TARGET = 1, MFX_QTRAIN_ADAM_M = 2, MFX_QTRAIN_ADAM_V = 3 };
 enum { MFX_QTRAIN_BAD_INDEX = 1, MFX_QTRAIN_BAD_ACTION = 2 };
+enum { MFX_QTARGET_MAX = 0, MFX_QTARGET_BOLTZMANN = 1 };
 int mfx_qtrain_create(int feature, int n_action, int use_mf, void **handle);
 int mfx_qtrain_destroy(void *handle);
 int mfx_qtrain_set_hyper(void *handle, double lr, double beta1, double beta2, double eps, double tau, double gamma);
+int mfx_qtrain_set_target(void *handle, int rule, float temperature);
 int mfx_qtrain_set_state(void *handle, int which, const float *d_blob, size_t n_floats, void *stream);
 int mfx_qtrain_get_state(void *handle, int which, float *d_out, size_t n_floats, void *stream);
 int mfx_qtrain_reset_optimizer(void *handle, void *stream);

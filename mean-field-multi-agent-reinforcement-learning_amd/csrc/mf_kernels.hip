@@ -2,6 +2,7 @@
 //
 //  * mean-action pooling   senario_battle.py:141  former_act_prob = mean(one_hot(acts)) (float64)
 //  * MF-Q target           algo/base.py:192-220   r + (1 - done) * Q_tgt(s', argmax Q_eval(s')) * gamma
+//  * Boltzmann MF-Q target (opt-in; the paper's v^MF, no reference line)   r + (1 - done) * sum_a pi(a) Q_tgt(s', a) * gamma
 //  * MF-AC returns         algo/ac.py:305-320     keep = keep * gamma + r[i], backwards per episode
 // Each follows the reference's numpy dtype rules and operation order (-ffp-contract=off).
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include <stdint.h>
 
 #include "mfx_common.h"
+#include "qsample.h"
 #include "../../include/magent_amd.h"
 
 namespace mfx {
@@ -50,6 +52,42 @@ __global__ void __launch_bounds__(256) k_mfq_target(const float* __restrict__ e_
     const double q = (double)t_q[(size_t)m * A + best];
     const double notdone = 1.0 - (done[m] ? 1.0 : 0.0);
     out[m] = (double)r[m] + (notdone * q) * gamma;
+}
+
+// The Boltzmann mean-field value target (tests/qtarget_ref.py restates it): one lane per sample.
+// w = the acting policy's weights on the eval net's row (q_weights_row: qsample.h, non-finite rule included),
+// v = sum_a f64(w[a]) f64(t_q[a]) / sum_a f64(w[a]) (q_soft_value), out = f64(r) + ((1 - done) * v) * gamma -- the form,
+// dtype rules and `done` reading of k_mfq_target.  d_T, when not null, is the temperature on the device (a captured
+// graph follows it); a temperature that is not finite and > 0 there makes every target (and weight) of the launch NaN.
+__global__ void __launch_bounds__(256) k_mfq_target_soft(const float* __restrict__ e_q, const float* __restrict__ t_q,
+                                                         const float* __restrict__ r, const uint8_t* __restrict__ done,
+                                                         int M, int A, double gamma, float T, const float* __restrict__ d_T,
+                                                         double* __restrict__ out, float* __restrict__ w_out) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const float Tv = d_T ? d_T[0] : T;
+    const bool ok = __builtin_fabsf(Tv) < __builtin_huge_valf() && Tv > 0.f;      // finite and > 0 (false for NaN)
+    const float* row = e_q + (size_t)m * A;
+    const float* tr = t_q + (size_t)m * A;
+    float x[kQSMaxA];
+#pragma unroll
+    for (int a = 0; a < kQSMaxA; ++a) x[a] = a < A ? row[a] : 0.f;
+    if (ok) {
+        float tot;
+        q_weights_row(x, A, Tv, tot);
+    } else {
+#pragma unroll
+        for (int a = 0; a < kQSMaxA; ++a) x[a] = __builtin_nanf("");
+    }
+    const double v = q_soft_value(x, A, [&](int a) { return tr[a]; });
+    const double notdone = 1.0 - (done[m] ? 1.0 : 0.0);
+    out[m] = (double)r[m] + (notdone * v) * gamma;
+    if (w_out) {
+        float* wr = w_out + (size_t)m * A;
+#pragma unroll
+        for (int a = 0; a < kQSMaxA; ++a)
+            if (a < A) wr[a] = x[a];
+    }
 }
 
 // One lane per episode: rewards[offsets[e] .. offsets[e+1]) are replaced by their discounted
@@ -101,6 +139,21 @@ MFX_API int mfx_mfq_target(const float* d_eq, const float* d_tq, const float* d_
     if (A < 1) return mfx::fail("mfq_target: A must be >= 1");
     if (M == 0) return 0;
     mfx::k_mfq_target<<<(M + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_eq, d_tq, d_r, d_done, M, A, gamma, d_out);
+    MFX_HIP(hipGetLastError());
+    return 0;
+}
+
+// The opt-in Boltzmann rule (include/magent_amd.h): d_T null: the host's T, refused unless finite and > 0.
+MFX_API int mfx_mfq_target_boltzmann(const float* d_eq, const float* d_tq, const float* d_r, const uint8_t* d_done, int M,
+                                     int A, double gamma, float T, const float* d_T, double* d_out, float* d_w,
+                                     void* stream) {
+    if (M < 0 || A < 2 || A > mfx::kQSMaxA)
+        return mfx::fail("mfq_target_boltzmann: M >= 0 and 2 <= A <= 32; got M %d, A %d", M, A);
+    if (!d_T && !(std::isfinite(T) && T > 0.f))
+        return mfx::fail("mfq_target_boltzmann: the temperature must be finite and > 0; got %g", (double)T);
+    if (M == 0) return 0;
+    mfx::k_mfq_target_soft<<<(M + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_eq, d_tq, d_r, d_done, M, A, gamma, T, d_T,
+                                                                             d_out, d_w);
     MFX_HIP(hipGetLastError());
     return 0;
 }

@@ -1,6 +1,7 @@
 // qsample.h -- the Boltzmann draw over one row of Q values: the opt-in acting mode "boltzmann" of the Q network
 // (k_qnet_head, k_qb16_head with kSample) and the stand-alone k_q_sample (qsample_kernels.hip).  One function, three
-// users, so the three give the same action and the same weights bit for bit on the same Q row.
+// users, so the three give the same action and the same weights bit for bit on the same Q row; its weight part
+// (q_weights_row) is also the policy of the Boltzmann value target.
 //
 // CONTRACT (include/magent_amd.h; tests/qsample_ref.py restates it in numpy).  For a row q[0..A) of f32 Q
 // values -- exactly the values the forward writes to d_q -- and a temperature T (finite, > 0: the host refuses others):
@@ -30,8 +31,13 @@ struct QSample {
     float* w;                       // [n][A] weights out, or null
 };
 
-// x[0..A): the row's Q values on entry (entries past A are not read), its weights on exit.  u: the row's uniform.
-__device__ __forceinline__ int q_sample_row(float (&x)[kQSMaxA], int A, float T, float u) {
+// The weights alone (the "weights" and "non-finite rows" lines of the contract): x[0..A) holds the row's Q values on
+// entry (entries past A are not read) and its weights on exit.  Returns -1 for a finite row, and the greedy action of
+// a row with a non-finite entry (whose weights are 1 there, 0 elsewhere).  Four users: the three draws through
+// q_sample_row, and the Boltzmann value target (k_mfq_target_soft, qt_row<kSoft>: DESIGN 7m), which weighs the
+// target net's values by exactly the acting policy's weights.  tot: the f32 sum of the weights in ascending action
+// order, accumulated as each weight is made (the draw's total; a caller that does not read it pays nothing).
+__device__ __forceinline__ int q_weights_row(float (&x)[kQSMaxA], int A, float T, float& tot) {
     float m = -__builtin_huge_valf();
     int bi = -1;
     bool finite = true;
@@ -48,10 +54,33 @@ __device__ __forceinline__ int q_sample_row(float (&x)[kQSMaxA], int A, float T,
             if (a < A) x[a] = a == bi ? 1.f : 0.f;
         return bi;
     }
-    float tot = 0.f;
+    tot = 0.f;
 #pragma unroll
     for (int a = 0; a < kQSMaxA; ++a)
         if (a < A) { x[a] = expf((x[a] - m) / T); tot += x[a]; }
+    return -1;
+}
+
+// The Boltzmann mean-field value of one row: v = sum_a f64(w[a]) f64(tq(a)) / sum_a f64(w[a]), both sums
+// in ascending action order in float64 (each product of two f32 values is exact there), one f64 division.  w: the
+// weights q_weights_row left.  A NaN or infinite tq(a) makes v NaN even where w[a] is 0.
+template <class TQ>
+__device__ __forceinline__ double q_soft_value(const float (&w)[kQSMaxA], int A, TQ tq) {
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int a = 0; a < kQSMaxA; ++a)
+        if (a < A) {
+            num += (double)w[a] * (double)tq(a);
+            den += (double)w[a];
+        }
+    return num / den;
+}
+
+// x[0..A): the row's Q values on entry (entries past A are not read), its weights on exit.  u: the row's uniform.
+__device__ __forceinline__ int q_sample_row(float (&x)[kQSMaxA], int A, float T, float u) {
+    float tot;
+    const int greedy = q_weights_row(x, A, T, tot);
+    if (greedy >= 0) return greedy;
     const float thr = u * tot;
     float run = 0.f;
     int pick = -1;

@@ -10,7 +10,7 @@
 //    3 k_qt_gemm<Conv2F>
 //    4 k_qt_gemm<DObsF>
 //    5 k_qt_head       the small layers of the three forwards, one workgroup per row
-//    6 k_qt_loss       y, d = y - q[a], dL/dq, back through Q-Value, Dense-Out, Dense2, Dense-Act-Prob (per row); stats
+//    6 k_qt_loss<rule> y (the max rule, or the opt-in Boltzmann value v^MF: mfx_qtrain_set_target), d = y - q[a], dL/dq, back through Q-Value, Dense-Out, Dense2, Dense-Act-Prob (per row); stats
 //    7 k_qt_dw_small   dW / db of every small layer and Dense-Obs's bias: one thread per element, rows in order
 //    8 k_qt_gemm<DObsB>    da2 = dh . Wd^T, masked by Conv2's ReLU
 //    9 k_qt_gemm<DWd>      dWd = a2^T . dh   (K = B)
@@ -36,6 +36,7 @@
 
 #include "mfx_common.h"
 #include "policy_gemm.h"
+#include "qsample.h"
 #include "../../include/magent_amd.h"
 
 namespace mfx {
@@ -68,6 +69,8 @@ struct QT {
     float* stats;                        // (loss, mean q[a]) of this minibatch
     double gamma;
     float lr_t, sqrt_bc2, omb1, omb2, eps, tau;
+    int rule;                            // MFX_QTARGET_MAX / MFX_QTARGET_BOLTZMANN: which k_qt_loss the host launches
+    float soft_T;                        // the Boltzmann rule's temperature (finite, > 0: set_target refuses others)
 };
 
 // jobs of the forward launches: 0 target(next rows), 1 eval(next rows), 2 eval(current rows)
@@ -455,27 +458,48 @@ __global__ void __launch_bounds__(128) k_qt_head(QT t) {
 }
 
 // ------------------------------------------------------------------------------------------ 6: target, loss, head backward
-// Row b's target y, q[a] and mask.  best: np.argmax of the eval net's next-state Q (first maximum; the first NaN wins,
-// as k_mfq_target); y = f32(f64(r) + ((1 - done) * f64(q_t[best])) * gamma).
+// Row b's target y, q[a] and mask.
+// kMaxRule: best = np.argmax of the eval net's next-state Q (first maximum; the first NaN wins, as k_mfq_target);
+//   y = f32(f64(r) + ((1 - done) * f64(q_t[best])) * gamma).
+// kSoftRule (opt-in; k_mfq_target_soft's arithmetic): the weights of qsample.h on the eval net's next-state Q
+//   (job 1) at t.soft_T, v = their float64 mean of the target net's next-state Q (job 0);
+//   y = f32(f64(r) + ((1 - done) * v) * gamma).
+constexpr int kMaxRule = MFX_QTARGET_MAX, kSoftRule = MFX_QTARGET_BOLTZMANN;
+
+template <int kRule>
 __device__ __forceinline__ void qt_row(const QT& t, int b, float& y, float& qa, float& mk) {
     const float* qe = t.q + ((size_t)t.B + b) * 32;
     const float* qt = t.q + (size_t)b * 32;
-    int best = 0;
-    float bv = qe[0];
-    if (!isnan(bv)) {
-        for (int k = 1; k < t.A; ++k) {
-            const float x = qe[k];
-            if (isnan(x)) { best = k; break; }
-            if (x > bv) { bv = x; best = k; }
+    if constexpr (kRule == kSoftRule) {
+        const int row = t.rows[b];
+        const double notdone = 1.0 - (t.term[row] ? 1.0 : 0.0);
+        float x[kQSMaxA];
+#pragma unroll
+        for (int a = 0; a < kQSMaxA; ++a) x[a] = a < t.A ? qe[a] : 0.f;
+        float tot;
+        q_weights_row(x, t.A, t.soft_T, tot);
+        const double v = q_soft_value(x, t.A, [&](int a) { return qt[a]; });
+        y = (float)((double)t.rew[row] + (notdone * v) * t.gamma);
+    } else {
+        int best = 0;
+        float bv = qe[0];
+        if (!isnan(bv)) {
+            for (int k = 1; k < t.A; ++k) {
+                const float x = qe[k];
+                if (isnan(x)) { best = k; break; }
+                if (x > bv) { bv = x; best = k; }
+            }
         }
+        const int row = t.rows[b];
+        const double notdone = 1.0 - (t.term[row] ? 1.0 : 0.0);
+        y = (float)((double)t.rew[row] + (notdone * (double)qt[best]) * t.gamma);
     }
     const int row = t.rows[b];
-    const double notdone = 1.0 - (t.term[row] ? 1.0 : 0.0);
-    y = (float)((double)t.rew[row] + (notdone * (double)qt[best]) * t.gamma);
     qa = t.q[((size_t)2 * t.B + b) * 32 + t.acts[b]];
     mk = t.mask[row] ? 1.f : 0.f;
 }
 
+template <int kRule>
 __global__ void __launch_bounds__(128) k_qt_loss(QT t) {
     __shared__ int cnt[128];
     __shared__ float red[2][128];
@@ -488,7 +512,7 @@ __global__ void __launch_bounds__(128) k_qt_loss(QT t) {
         float l = 0.f, qs = 0.f;
         for (int i = tid; i < B; i += 128) {
             float y, qa, mk;
-            qt_row(t, i, y, qa, mk);
+            qt_row<kRule>(t, i, y, qa, mk);
             const float d = y - qa;
             l += d * d * mk;
             qs += qa;
@@ -507,7 +531,7 @@ __global__ void __launch_bounds__(128) k_qt_loss(QT t) {
         t.stats[1] = qs / (float)B;
     }
     float y, qa, mk;
-    qt_row(t, b, y, qa, mk);
+    qt_row<kRule>(t, b, y, qa, mk);
     const int a = t.acts[b];
     const float gq = (-2.f * (y - qa) * mk) / sm;   // dL/dq[a]
     const float* w = t.eval;
@@ -614,6 +638,8 @@ struct QTrain {
     float* stats_scratch = nullptr;
     double lr = 1e-4, beta1 = 0.9, beta2 = 0.999, eps = 1e-8, tau = 0.005, gamma = 0.95;
     long long step = 0;
+    int rule = MFX_QTARGET_MAX;        // mfx_qtrain_set_target
+    float soft_T = 0.1f;
 };
 
 constexpr size_t kFwRow = kTC1 + kTC2 + 256 + 32 + 64 + 32 + 128 + 64 + 32;       // per (job, row)
@@ -650,6 +676,7 @@ int qt_fill(QTrain* h, const mfx_qtrain_ring* ring, long long n, const int64_t* 
     t.demb = f; f += b * 32; t.dp2 = f; f += b * 32; t.dp1 = f; f += b * 64; t.dc2 = f; f += b * kTC2; t.dc1 = f;
     t.stats = d_stats ? d_stats : h->stats_scratch;
     t.gamma = h->gamma;
+    t.rule = h->rule; t.soft_T = h->soft_T;
     t.omb1 = (float)(1.0 - h->beta1); t.omb2 = (float)(1.0 - h->beta2); t.eps = (float)h->eps; t.tau = (float)h->tau;
     *out = t;
     return 0;
@@ -700,7 +727,8 @@ int qt_gradient(const QT& t, hipStream_t st) {
     qt_gemm<1, 4, Conv2F>(t, B * 81, 32, 3, st);
     qt_gemm<4, 1, DObsF>(t, B, 256, 3, st);
     k_qt_head<<<dim3(B, 3), 128, 0, st>>>(t);
-    k_qt_loss<<<B, 128, 0, st>>>(t);
+    if (t.rule == kSoftRule) k_qt_loss<kSoftRule><<<B, 128, 0, st>>>(t);
+    else k_qt_loss<kMaxRule><<<B, 128, 0, st>>>(t);
     QSegs sg;
     qt_segments(t, &sg);
     k_qt_dw_small<<<(sg.total + 255) / 256, 256, 0, st>>>(t, sg);
@@ -759,6 +787,21 @@ MFX_API int mfx_qtrain_set_hyper(void* handle, double lr, double beta1, double b
         !(tau >= 0.0 && tau <= 1.0))
         return fail("qtrain_set_hyper: lr >= 0, beta in [0, 1), eps > 0 (an entry with g = m = v = 0 must divide by it), tau in [0, 1]");
     h->lr = lr; h->beta1 = beta1; h->beta2 = beta2; h->eps = eps; h->tau = tau; h->gamma = gamma;
+    return 0;
+}
+
+MFX_API int mfx_qtrain_set_target(void* handle, int rule, float temperature) {
+    auto* h = static_cast<QTrain*>(handle);
+    if (!h) return fail("qtrain: null handle");
+    if (rule != MFX_QTARGET_MAX && rule != MFX_QTARGET_BOLTZMANN)
+        return fail("qtrain_set_target: rule %d (0 max, 1 boltzmann)", rule);
+    if (rule == MFX_QTARGET_BOLTZMANN) {
+        if (h->A < 2) return fail("qtrain_set_target: the boltzmann rule takes 2 <= n_action <= 32; the handle has %d", h->A);
+        if (!(std::isfinite(temperature) && temperature > 0.f))
+            return fail("qtrain_set_target: the temperature must be finite and > 0; got %g", (double)temperature);
+        h->soft_T = temperature;
+    }
+    h->rule = rule;
     return 0;
 }
 

@@ -5,7 +5,6 @@ Inputs may be numpy arrays (the reference's call sites) or device tensors (the b
 outputs follow the reference: act -> int32 numpy, calc_target_q -> float64, train -> (loss, stats).
 """
 import copy
-import math
 import zlib
 
 import numpy as np
@@ -31,12 +30,8 @@ def weights_key(net, gen=0):
 EXPLORE = ("greedy", "boltzmann")       # ValueNet.explore
 
 
-def check_temperature(t):
-    """The Boltzmann temperature as a float; ValueError unless it is finite and > 0 (the library refuses it too)."""
-    t = float(t)
-    if not (math.isfinite(t) and t > 0.0):
-        raise ValueError("explore 'boltzmann': the temperature (eps) must be finite and > 0, got %r" % (t,))
-    return t
+TARGET_RULES = ("max", "boltzmann")     # ValueNet.target_rule
+check_temperature = mf.check_temperature    # finite and > 0, else ValueError: one rule for acting and for the target
 
 
 class ValueNet:
@@ -44,6 +39,8 @@ class ValueNet:
     act_precision = "f32"       # act_dev's HIP forward: "f32", or "bf16" operands (mfrl_amd.policy); training stays f32
     _train_backend = "torch"    # train_batches: "torch" (the graph below), or "hip" (mfrl_amd.qtrain, csrc/qtrain_kernels.hip)
     _explore = "greedy"         # act_dev / act_rollout: "greedy" (the reference's argmax), or "boltzmann" (csrc/qsample.h)
+    _target_rule = "max"        # training target: "max" (the reference's rule), or "boltzmann" (the paper's v^MF)
+    target_temperature = None   # target_rule "boltzmann": None = self.temperature (the last acting eps); a float overrides it
 
     def __init__(self, sess, env, handle, name, update_every=5, use_mf=False, learning_rate=1e-4, tau=0.005,
                  gamma=0.95):
@@ -82,7 +79,7 @@ class ValueNet:
         stored) or "boltzmann" (opt-in): the action is drawn from softmax(q / T) with T = the call's eps, by the
         contract of csrc/qsample.h -- the uniform of a row is the counter hash of (self.seed, the count of acting
         calls, the group, the row), so np.random is not consumed and seeded runs repeat.  Training is the same in both
-        modes (the target stays the reference's max rule)."""
+        modes: the target is chosen by target_rule, on its own."""
         return self._explore
 
     @explore.setter
@@ -90,6 +87,34 @@ class ValueNet:
         if value not in EXPLORE:
             raise ValueError("explore %r (one of %s)" % (value, ", ".join(EXPLORE)))
         self._explore = value
+
+    @property
+    def target_rule(self):
+        """What calc_target_q_dev and train_batches bootstrap from: "max" (the default and the reference's rule: the
+        target net's value of the eval net's greedy next action) or "boltzmann" (opt-in; the paper's mean-field value
+        v^MF = sum_a pi(a) Q_target(s', a) with pi = softmax(Q_eval(s') / T): mfrl_amd.mf.mfq_target_boltzmann, and
+        QTrainHIP.set_target on the "hip" backend).  pi's weights are exactly those the "boltzmann" explore mode draws
+        from.  T = target_temperature, or self.temperature (the last acting eps) while that is None; it must be finite
+        and > 0 when a target is computed.  Setting another rule drops a captured training graph."""
+        return self._target_rule
+
+    @target_rule.setter
+    def target_rule(self, value):
+        if value not in TARGET_RULES:
+            raise ValueError("target_rule %r (one of %s)" % (value, ", ".join(TARGET_RULES)))
+        if value != self._target_rule:
+            self._graph = None
+        self._target_rule = value
+
+    def _target_T(self):
+        """The Boltzmann target's temperature for the call at hand (ValueError unless finite and > 0)."""
+        T = self.temperature if self.target_temperature is None else self.target_temperature
+        return mf.check_temperature(T, "target_rule 'boltzmann': the temperature (target_temperature, else the last eps)")
+
+    def _target(self, e_q, t_q, rewards, dones, temperature):
+        if self._target_rule == "boltzmann":
+            return mf.mfq_target_boltzmann(e_q, t_q, rewards, dones, self.gamma, temperature)
+        return mf.mfq_target(e_q, t_q, rewards, dones, self.gamma)
 
     @property
     def train_backend(self):
@@ -133,8 +158,9 @@ class ValueNet:
         prob = self._prob(kwargs, len(obs))
         t_q = self.target_net(obs, feat, prob)
         e_q = self.eval_net(obs, feat, prob)
-        return mf.mfq_target(e_q.float().contiguous(), t_q.float().contiguous(), as_dev(kwargs["rewards"]),
-                             as_dev(kwargs["dones"], torch.uint8), self.gamma)
+        return self._target(e_q.float().contiguous(), t_q.float().contiguous(), as_dev(kwargs["rewards"]),
+                            as_dev(kwargs["dones"], torch.uint8),
+                            self._target_T() if self._target_rule == "boltzmann" else None)
 
     @torch.no_grad()
     def update(self):
@@ -162,6 +188,13 @@ class ValueNet:
         idx_d = torch.as_tensor(idx, device="cuda")
         nxt_d = torch.as_tensor(nxt, device="cuda")
         stats = torch.zeros((batch_num, 2), dtype=torch.float32, device="cuda")
+        if self._target_rule == "boltzmann":
+            # the captured graph reads the temperature from a static device tensor, refilled at every call: eps moves
+            # from round to round, and a graph captured in one round must not go on training at that round's value
+            T = self._target_T()
+            if getattr(self, "_s_T", None) is None:
+                self._s_T = torch.zeros(1, dtype=torch.float32, device="cuda")
+            self._s_T.fill_(T)
         if self._graph is None:
             self._s_idx = torch.zeros(B, dtype=torch.int64, device="cuda")
             self._s_nxt = torch.zeros(B, dtype=torch.int64, device="cuda")
@@ -208,6 +241,10 @@ class ValueNet:
             self._qtrain_key = None
         tr = self._qtrain
         tr.set_hyper(self.lr, tau=self.tau, gamma=self.gamma)      # the model's current values, as the torch path reads them
+        if self._target_rule == "boltzmann":
+            tr.set_target("boltzmann", self._target_T())
+        elif tr.target_rule != "max":
+            tr.set_target("max")
         key = (weights_key(self.eval_net, self._wgen), weights_key(self.target_net, self._wgen))
         if key != self._qtrain_key:
             tr.load(self.eval_net, self.target_net)
@@ -245,7 +282,8 @@ class ValueNet:
         with torch.no_grad():
             t_q = self.target_net(obs_n, feat_n, prob_n)
             e_qn = self.eval_net(obs_n, feat_n, prob_n)
-            target = mf.mfq_target(e_qn.float().contiguous(), t_q.float().contiguous(), rew, done, self.gamma)
+            target = self._target(e_qn.float().contiguous(), t_q.float().contiguous(), rew, done,
+                                  self._s_T if self._target_rule == "boltzmann" else None)
         e_q = self.eval_net(obs, feat, prob)
         e_q_max = e_q.gather(1, acts.reshape(-1, 1)).reshape(-1)
         loss = torch.sum(torch.square(target.float() - e_q_max) * mask) / torch.sum(mask)

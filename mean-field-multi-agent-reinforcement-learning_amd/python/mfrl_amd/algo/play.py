@@ -264,7 +264,11 @@ def play_rollout_episodes(eng, n_round, map_size, max_steps, models, print_every
 
 def _act_rollout(model, eng, g, eps):
     """model.act_rollout for one group of a device-loop round: a model that explores (ValueNet.explore other than
-    "greedy") gets the round's eps as its temperature; every other model is called as it always was."""
+    "greedy") gets the round's eps as its temperature; every other model is called as it always was.  A model that
+    trains on the Boltzmann target (ValueNet.target_rule) records the round's eps even while it acts greedily, as
+    act_dev records it: its training reads model.temperature."""
+    if getattr(model, "target_rule", "max") != "max":
+        model.temperature = eps
     if getattr(model, "explore", "greedy") != "greedy":
         model.act_rollout(eng, g, eps=eps)
     else:

@@ -4,10 +4,12 @@
     mfq_target(e_q, t_q, rewards, dones, g)  algo/base.py:192-220 (ValueNet.calc_target_q), float64
     mfac_returns(rewards, offsets, values, g) algo/ac.py:305-320 (discounted returns, float64 running
                                              return stored as float32: the reference's NumPy-1 rules)
+    mfq_target_boltzmann(e_q, t_q, r, d, g, T)  the opt-in Boltzmann value target (the paper's v^MF), float64
     q_sample(q, temperature, seed, step)     the Boltzmann draw over Q rows (csrc/qsample.h): the opt-in exploration
                                              of the Q models; no counterpart in the reference, whose act is greedy
 """
 import ctypes
+import math
 
 import torch
 
@@ -61,6 +63,50 @@ def mfq_target(e_q, t_q, rewards, dones, gamma=0.95):
     check(L.mfx_mfq_target(_p(e_q.contiguous()), _p(t_q.contiguous()), _p(rewards.contiguous()), _p(d), M, A,
                            ctypes.c_double(gamma), _p(out), _stream()), "mfx_mfq_target")
     return out
+
+
+def check_temperature(t, what="explore 'boltzmann': the temperature (eps)"):
+    """A Boltzmann temperature as a float; ValueError unless it is finite and > 0 (the library refuses it too)."""
+    t = float(t)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError("%s must be finite and > 0, got %r" % (what, t))
+    return t
+
+
+def mfq_target_boltzmann(e_q, t_q, rewards, dones, gamma, temperature, want_w=False):
+    """The opt-in Boltzmann mean-field value target (k_mfq_target_soft; the contract of include/magent_amd.h, DESIGN 7m,
+    restated in tests/qtarget_ref.py): target = r + (1 - done) * v * gamma, float64 [M], with v the mean of t_q under
+    the acting weights of q_sample on e_q (expf((e_q - max e_q) / temperature), its non-finite rule included), summed
+    in float64.  e_q, t_q float32 [M, A], 2 <= A <= 32, rewards float32 [M], dones bool / uint8 [M]: the dtype and shape
+    refusals of mfq_target.
+
+    temperature: a Python float, finite and > 0 (ValueError otherwise; nothing is launched), or a one-element float32
+    CUDA tensor read by the kernel when it runs -- a captured graph follows what is written into it; a value there
+    that is not finite and > 0 makes every target of the launch NaN.  want_w: (target, weights float32 [M, A])."""
+    _dtype("mfq_target_boltzmann", e_q=(e_q, torch.float32), t_q=(t_q, torch.float32), rewards=(rewards, torch.float32))
+    M, A = e_q.shape
+    if t_q.shape != (M, A) or rewards.shape != (M,) or dones.shape != (M,):
+        raise ValueError("mfq_target_boltzmann: e_q %s, t_q %s, rewards %s, dones %s" % tuple(
+            tuple(x.shape) for x in (e_q, t_q, rewards, dones)))
+    if not 2 <= A <= 32:
+        raise ValueError("mfq_target_boltzmann: 2 <= A <= 32, got %d" % A)
+    null = ctypes.c_void_p()
+    if isinstance(temperature, torch.Tensor):
+        _dtype("mfq_target_boltzmann", temperature=(temperature, torch.float32))
+        if temperature.numel() != 1 or not temperature.is_cuda:
+            raise ValueError("mfq_target_boltzmann: a tensor temperature is one float32 element on the device")
+        T, d_T = 0.0, _p(temperature)
+    else:
+        T, d_T = check_temperature(temperature, "mfq_target_boltzmann: the temperature"), null
+    out = torch.empty(M, dtype=torch.float64, device=e_q.device)
+    w = torch.empty((M, A), dtype=torch.float32, device=e_q.device) if want_w else None
+    d = dones.to(torch.uint8).contiguous()
+    L = lib()
+    L.mfx_mfq_target_boltzmann.restype = ctypes.c_int
+    check(L.mfx_mfq_target_boltzmann(_p(e_q.contiguous()), _p(t_q.contiguous()), _p(rewards.contiguous()), _p(d), M, A,
+                                     ctypes.c_double(gamma), ctypes.c_float(T), d_T, _p(out), _p(w) if want_w else null,
+                                     _stream()), "mfx_mfq_target_boltzmann")
+    return (out, w) if want_w else out
 
 
 def q_sample(q, temperature, seed, step, group=0, rows=None, want_w=False):

@@ -20,6 +20,7 @@ from .policy import blob_layout, pack_qnet, unpack_qnet
 _P = ctypes.c_void_p
 EVAL, TARGET, ADAM_M, ADAM_V = 0, 1, 2, 3
 MAX_BATCH = 4096
+TARGET_RULES = {"max": 0, "boltzmann": 1}      # MFX_QTARGET_MAX / MFX_QTARGET_BOLTZMANN
 _ERRORS = {1: "a sample index outside [0, nb_entries)", 2: "a replay action outside [0, n_action)"}
 
 
@@ -48,7 +49,7 @@ class QTrainHIP:
                              "most 32 actions; got %r, %r, %r" % (tuple(view_space), tuple(feature_space), num_actions))
         self.F, self.A, self.use_mf = int(feature_space[0]), int(num_actions), bool(use_mf)
         L = lib()
-        for fn in ("create", "destroy", "set_hyper", "set_state", "get_state", "reset_optimizer", "step_count", "grads",
+        for fn in ("create", "destroy", "set_hyper", "set_target", "set_state", "get_state", "reset_optimizer", "step_count", "grads",
                    "run", "error"):
             getattr(L, "mfx_qtrain_" + fn).restype = ctypes.c_int
         self._L = L
@@ -56,6 +57,7 @@ class QTrainHIP:
         hdl = _P()
         check(L.mfx_qtrain_create(self.F, self.A, int(self.use_mf), ctypes.byref(hdl)), "mfx_qtrain_create")
         self.handle = hdl
+        self.target_rule = "max"
         self.set_hyper(lr, betas, eps, tau, gamma)
 
     def __del__(self):
@@ -67,6 +69,18 @@ class QTrainHIP:
         D = ctypes.c_double
         check(self._L.mfx_qtrain_set_hyper(self.handle, D(lr), D(betas[0]), D(betas[1]), D(eps), D(tau), D(gamma)),
               "mfx_qtrain_set_hyper")
+
+    def set_target(self, rule, temperature=0.1):
+        """The rule of the minibatches' target y, for the grads / run calls that follow: "max" (the default: the target
+        net's value of the eval net's greedy next action) or "boltzmann" (opt-in, DESIGN 7m: the target net's next-state
+        values averaged under the weights expf((q_eval - max q_eval) / temperature), as mf.mfq_target_boltzmann).
+        temperature is read only for "boltzmann" and must be finite and > 0 (the library refuses others); a refusal
+        leaves the handle as it was."""
+        if rule not in TARGET_RULES:
+            raise ValueError("QTrainHIP.set_target: rule %r (one of %s)" % (rule, ", ".join(TARGET_RULES)))
+        check(self._L.mfx_qtrain_set_target(self.handle, TARGET_RULES[rule], ctypes.c_float(temperature)),
+              "mfx_qtrain_set_target")
+        self.target_rule = rule
 
     # ------------------------------------------------------------------ state
     def set_state(self, which, blob):

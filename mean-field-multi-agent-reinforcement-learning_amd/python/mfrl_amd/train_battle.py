@@ -8,6 +8,7 @@
     python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes --ac_train_backend hip ...   # + the HIP step
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --render --watch 0 63 ...   # + frames of two envs
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann ...   # sample from softmax(q / eps)
+    python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann --target boltzmann ...   # + the paper's v^MF target
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -71,7 +72,14 @@ def main(argv=None):
     parser.add_argument("--explore", type=str, choices=["greedy", "boltzmann"], default="greedy",
                         help="mfq / il: how the models act while they play -- greedy (the reference: argmax q, the eps "
                              "schedule unused) or boltzmann (drawn from softmax(q / eps), eps from the schedule)")
+    parser.add_argument("--target", type=str, choices=["max", "boltzmann"], default="max",
+                        help="mfq / il: what training bootstraps from -- max (the reference: the target net's value of the "
+                             "greedy next action) or boltzmann (the paper's mean-field value: the target net's values "
+                             "averaged under softmax(q / eps), eps from the schedule); either --train_backend")
     args = parser.parse_args(argv)
+    if args.target != "max" and args.algo not in ("mfq", "il"):
+        parser.error("--target boltzmann bootstraps from the Q values: --algo mfq or il (ac / mfac train on their "
+                     "returns)")
     if args.explore != "greedy" and args.algo not in ("mfq", "il"):
         parser.error("--explore boltzmann samples from the Q values: --algo mfq or il (ac / mfac sample from their "
                      "policy already)")
@@ -125,6 +133,8 @@ def main(argv=None):
             m.act_precision = args.act_precision
         if args.explore != "greedy":
             m.explore = args.explore
+        if args.target != "max":
+            m.target_rule = args.target
     play_handle = play
     if args.envs > 1:
         from .battle import BattleBatch
