@@ -264,6 +264,47 @@ int mfx_mfq_target_boltzmann(const float *d_eq, const float *d_tq, const float *
 int mfx_mfac_returns(float *d_rew, const int64_t *d_offsets, const float *d_value, int n_ep, double gamma,
                      int numpy1, void *stream);
 
+/* ---------------------------------------------------------------- part 4b: neighbourhood mean action (opt-in) */
+/* The paper's mean action (arXiv 1802.05438 eq. 6), a_bar_j = 1 / |N(j)| sum_{k in N(j)} a_k over agent j's own
+ * neighbours, where mfx_mean_action, the rollout's mean buffer and the reference give every agent of a group the
+ * group-wide mean (csrc/neighbor_kernels.hip; tests/neighbor_mean_ref.py restates it).  For a list of n
+ * members of one group with positions (x_j, y_j) and actions a_j, radius R >= 0:
+ *   N_R(j)     the members k with max(|x_k - x_j|, |y_k - y_j|) <= R, j itself included: |N_R(j)| >= 1, no NaN case
+ *   out[j][a]  (float)((double)(members of N_R(j) with action a) / (double)|N_R(j)|), a < n_action; an action outside
+ *              [0, n_action) is counted in no entry while the divisor stays (mfx_mean_action's rule)
+ * Integer counts and one float64 division per entry: bitwise reproducible, no tolerance.  One workgroup per list on
+ * a persistent grid scans, per member, the window of a W x H byte grid kept in LDS; plain vector stores only.
+ * Limits: 1 <= n_action <= 64, R >= 0, W * H + 5 * rowcap + 1040 bytes of LDS <= 160 KiB (256 x 256 with 4096 rows
+ * fits; 512 x 512 does not).  Anything else returns -1 (mfx_last_error names the limit) and nothing is launched.
+ *
+ * mfx_neighbor_mean  the definition on a compact list: d_pos [B][rowcap][2] (x, y), d_actions [B][rowcap], d_counts
+ *                    [B] (capped at rowcap, a negative one reads as 0) -> d_out [B][rowcap][n_action] float32; rows
+ *                    at and past the count are left as they are.  The positions of one list must be distinct cells
+ *                    inside the map, as the engine guarantees for its agents: this is the caller's contract and is
+ *                    not checked (a position outside the map gets a row of zeros and counts for nobody).
+ * The rollout forms run the same device code behind another loader, for group `group` of an engine behind
+ * mfx_battle_rollout_init, on the engine's stream; nothing is read back.  d_out [E][rowcap][n_action] float32 and
+ * d_state (2 * E int32: prev_num [E], prev_episode [E]) are the caller's; one workgroup owns an env's entries.
+ *   mfx_neighbor_mean_reset    after the policy observe: rows j < group_num[e][group] zero (the reference starts an
+ *                              episode from a zero mean, senario_battle.py:89), prev_num = group_num, prev_episode =
+ *                              (int)stats[e][0].
+ *   mfx_neighbor_mean_rollout  once after every mfx_battle_rollout_policy_step.  Members are the survivors of the
+ *                              step, the rows j < group_num[e][group] of the new observation: (x, y) = (rint(feat[F - 2]
+ *                              W), rint(feat[F - 1] H)) of feature row j (the observation writes (float)x / (float)W
+ *                              there: exact); the action of survivor j is the action-buffer entry of the j-th row
+ *                              with alive != 0 among the first prev_num rows (actions and alive keep the order of
+ *                              before clear_dead).  Agents that died in the step have no position and count for
+ *                              nobody.  An env whose episode number differs from prev_episode restarted in the
+ *                              step: its rows j < group_num are zero.  Rows j >= group_num are left as they are.
+ *                              Then prev_num and prev_episode are rewritten, in the same launch.
+ * Both refuse a group whose features carry no position (minimap_mode off).  With no death in the step and R >= max(W,
+ * H) every row equals the rollout's mean_action[e][group][a] cast to float, bit for bit; with R = 0 it is the one-hot
+ * row of the agent's own action. */
+int mfx_neighbor_mean(const int32_t *d_pos, const int32_t *d_actions, const int32_t *d_counts, int B, int rowcap,
+                      int n_action, int radius, int W, int H, float *d_out, void *stream);
+int mfx_neighbor_mean_reset(void *game, int group, float *d_out, int32_t *d_state);
+int mfx_neighbor_mean_rollout(void *game, int group, int radius, float *d_out, int32_t *d_state);
+
 /* ---------------------------------------------------------------- part 5: policy forward */
 /* The Q network of ValueNet._construct_net (algo/base.py:123-183) and its greedy act (:228-254), forward
  * only, f32 MFMA (csrc/policy_kernels.hip); the Battle view (13 x 13 x 7), features F <= 256, n_action <= 32.
@@ -317,6 +358,18 @@ int mfx_qnet_act_rollout_sample(void *handle, const float *d_view, const float *
                                 const double *d_mean, int mean_stride, int E, int G, int g, int rowcap, int32_t *d_rows,
                                 int32_t *d_total, int32_t *d_act, float temperature, uint32_t seed, uint32_t step,
                                 void *stream);
+/* mfx_qnet_act_rollout / _sample with a mean action per agent (the neighbourhood mean of part 4b) in
+ * place of the env's row of d_mean: rollout row e * rowcap + j reads d_prob_rows [E][rowcap][A] float32 (A the
+ * handle's n_action) at its own index.  Everything else -- the row list, the precisions, the draw and its uniform
+ * (seed, step, g, e * rowcap + j), the rows written -- is the call's above: with d_prob_rows[e][j] = (float)
+ * d_mean[e][g] for every live row the actions are bit for bit the same. */
+int mfx_qnet_act_rollout_rows(void *handle, const float *d_view, const float *d_feat, const int32_t *d_counts,
+                              const float *d_prob_rows, int E, int G, int g, int rowcap, int32_t *d_rows,
+                              int32_t *d_total, int32_t *d_act, void *stream);
+int mfx_qnet_act_rollout_rows_sample(void *handle, const float *d_view, const float *d_feat, const int32_t *d_counts,
+                                     const float *d_prob_rows, int E, int G, int g, int rowcap, int32_t *d_rows,
+                                     int32_t *d_total, int32_t *d_act, float temperature, uint32_t seed, uint32_t step,
+                                     void *stream);
 /* The draw alone on a Q table in memory (k_q_sample): d_q [n][A] f32, 2 <= A <= 32 -> d_act [n], d_w [n][A] (either
  * may be null); row i drawn with (seed, step, group, i) -- mfx_q_sample_rows: (seed, step, group, d_rows[i]), d_rows
  * null: i. */
@@ -434,6 +487,12 @@ int mfx_collect_begin(const mfx_collect_src *src, const mfx_collect_dst *dst, in
                       int64_t *d_state, void *stream);
 int mfx_collect_end(const mfx_collect_src *src, const mfx_collect_dst *dst, const int32_t *d_rows,
                     const int32_t *d_total, int64_t *d_state, int64_t id_stride, void *stream);
+/* mfx_collect_begin with a mean action per agent (part 4b): list entry k = row j of env e takes its prob
+ * from d_prob_rows[(e * rowcap + j) * n_action + a] (float32 [E][rowcap][n_action] of the group, copied bit for bit)
+ * where mfx_collect_begin casts the env's row of src->mean; src->mean is not read.  dst->prob must not be null.
+ * Everything else, mfx_collect_end and mfx_collect_end_linked included, is unchanged. */
+int mfx_collect_begin_rows(const mfx_collect_src *src, const mfx_collect_dst *dst, const float *d_prob_rows,
+                           int32_t *d_rows, int32_t *d_total, int64_t *d_state, void *stream);
 /* (episode * n_envs + env) * id_stride + id: injective over env < n_envs, episode >= 0, id < id_stride (host) */
 int64_t mfx_collect_key(int64_t env, int64_t episode, int64_t id, int64_t n_envs, int64_t id_stride);
 

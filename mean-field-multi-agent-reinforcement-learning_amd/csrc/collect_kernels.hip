@@ -61,10 +61,13 @@ struct CollectRow {
     int64_t ep;                //         the episode number
 };
 
-template <bool kProb>
+// kProb: 0 no prob column, 1 the env's mean action (s.mean, float64), 2 the row's own (prob_rows [E][rowcap][n_action]
+// float32: the neighbourhood mean, neighbor_kernels.hip).
+template <int kProb>
 __global__ void __launch_bounds__(256) k_collect_begin(mfx_collect_src s, mfx_collect_dst d,
                                                        const int32_t* __restrict__ rows,
-                                                       const int32_t* __restrict__ total, int64_t* state) {
+                                                       const int32_t* __restrict__ total, int64_t* state,
+                                                       const float* __restrict__ prob_rows) {
     const int lane = threadIdx.x & 63;
     const int count = *total;
     const int64_t n = state[0];
@@ -91,7 +94,8 @@ __global__ void __launch_bounds__(256) k_collect_begin(mfx_collect_src s, mfx_co
         if (lane < nt) r.t = vp[4 * nq + lane];
         if (lane < s.feat_floats)
             r.f = reinterpret_cast<const uint32_t*>(s.feat)[(size_t)row * s.feat_floats + lane];
-        if (kProb && lane < s.n_action) r.p = (float)s.mean[eg * s.mean_stride + lane];
+        if (kProb == 1 && lane < s.n_action) r.p = (float)s.mean[eg * s.mean_stride + lane];
+        if (kProb == 2 && lane < s.n_action) r.p = prob_rows[(size_t)row * s.n_action + lane];
         if (lane == 0) {
             r.a = s.actions[eg * s.rowcap + j];
             r.ep = (int64_t)s.stats[(size_t)e * 4];
@@ -229,7 +233,7 @@ __global__ void k_collect_reset(int64_t* state, int64_t n) {
 }
 
 static int collect_shape(const mfx_collect_src* s, const mfx_collect_dst* d, const void* rows, const void* total,
-                         const void* state) {
+                         const void* state, const float* prob_rows = nullptr) {
     if (!s || !d || !rows || !total || !state) return fail("collect: null argument");
     if (s->n_envs < 1 || s->n_groups < 1 || s->group < 0 || s->group >= s->n_groups || s->rowcap < 1)
         return fail("collect: bad batch shape");
@@ -237,8 +241,10 @@ static int collect_shape(const mfx_collect_src* s, const mfx_collect_dst* d, con
         return fail("collect: view rows of 1..%d floats, got %d", 64 * 4 * kColQ + 3, s->view_floats);
     if (s->feat_floats < 1 || s->feat_floats > kColNarrow)
         return fail("collect: feature rows of 1..%d floats, got %d", kColNarrow, s->feat_floats);
-    if (d->prob && (s->n_action < 1 || s->n_action > kColNarrow || s->n_action > s->mean_stride || !s->mean))
+    if (d->prob && !prob_rows && (s->n_action < 1 || s->n_action > kColNarrow || s->n_action > s->mean_stride || !s->mean))
         return fail("collect: mean actions of 1..%d entries within the stride, got %d", kColNarrow, s->n_action);
+    if (prob_rows && (!d->prob || s->n_action < 1 || s->n_action > kColNarrow))
+        return fail("collect: per-row mean actions need a prob column and 1..%d entries, got %d", kColNarrow, s->n_action);
     if (!s->view || !s->feat || !s->actions || !s->rewards || !s->stats || !s->counts || !s->ids || !s->alive)
         return fail("collect: a rollout buffer is missing");
     if (!d->obs || !d->feat || !d->act || !d->rew || !d->term || !d->key || d->capacity < 0)
@@ -261,19 +267,32 @@ MFX_API int mfx_collect_reset(int64_t* d_state, int64_t n, void* stream) {
     return 0;
 }
 
-MFX_API int mfx_collect_begin(const mfx_collect_src* src, const mfx_collect_dst* dst, int32_t* d_rows, int32_t* d_total,
-                              int64_t* d_state, void* stream) {
-    MFX_CHECK(collect_shape(src, dst, d_rows, d_total, d_state));
+static int collect_begin(const mfx_collect_src* src, const mfx_collect_dst* dst, const float* d_prob_rows, int32_t* d_rows,
+                         int32_t* d_total, int64_t* d_state, void* stream) {
+    MFX_CHECK(collect_shape(src, dst, d_rows, d_total, d_state, d_prob_rows));
     hipStream_t st = (hipStream_t)stream;
     MFX_HIP(launch_rollout_rows(src->counts, src->n_envs, src->n_groups, src->group, src->rowcap, d_rows, d_total, st));
     // persistent-sized grid for the upper bound of the list (the count stays on the device): three workgroups per
     // CU, k_rows_pipe's best for one wide column (profiles/r06_replay_ab.txt)
     const int64_t wgs = ((int64_t)src->n_envs * src->rowcap + 3) / 4, cap = (int64_t)device_cus() * 3;
     const int grid = (int)(wgs < cap ? wgs : cap);
-    if (dst->prob) k_collect_begin<true><<<grid, 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state);
-    else k_collect_begin<false><<<grid, 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state);
+    if (d_prob_rows) k_collect_begin<2><<<grid, 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state, d_prob_rows);
+    else if (dst->prob) k_collect_begin<1><<<grid, 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state, nullptr);
+    else k_collect_begin<0><<<grid, 256, 0, st>>>(*src, *dst, d_rows, d_total, d_state, nullptr);
     MFX_HIP(hipGetLastError());
     return 0;
+}
+
+MFX_API int mfx_collect_begin(const mfx_collect_src* src, const mfx_collect_dst* dst, int32_t* d_rows, int32_t* d_total,
+                              int64_t* d_state, void* stream) {
+    return collect_begin(src, dst, nullptr, d_rows, d_total, d_state, stream);
+}
+
+// mfx_collect_begin with the prob of a row taken from its own entry of d_prob_rows [E][rowcap][n_action] float32.
+MFX_API int mfx_collect_begin_rows(const mfx_collect_src* src, const mfx_collect_dst* dst, const float* d_prob_rows,
+                                   int32_t* d_rows, int32_t* d_total, int64_t* d_state, void* stream) {
+    if (!d_prob_rows) return fail("collect_begin_rows: null prob rows");
+    return collect_begin(src, dst, d_prob_rows, d_rows, d_total, d_state, stream);
 }
 
 MFX_API int mfx_collect_end(const mfx_collect_src* src, const mfx_collect_dst* dst, const int32_t* d_rows,

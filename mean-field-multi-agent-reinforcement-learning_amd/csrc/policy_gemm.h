@@ -253,10 +253,12 @@ __device__ __forceinline__ float relu_unit(const f32x4* acc, const float* __rest
 }
 
 // Compact agent i -> (view row, action slot, prob row): rows == null: (i, i, i); else row = rows[i]
-// = e * rowcap + j of a rollout buffer, action slot e * act_env + act_off + j, prob row e.
+// = e * rowcap + j of a rollout buffer, action slot e * act_env + act_off + j, prob row e -- or, with prob_by_row
+// (a mean action per agent: the neighbourhood mean, neighbor_kernels.hip), the rollout row e * rowcap + j itself.
 struct QRowMap {
     const int32_t* rows;
     int rowcap, act_env, act_off;
+    int prob_by_row;
 };
 
 // The compact row list of one group of a rollout batch (policy_kernels.hip k_qnet_rows): rows e * rowcap + j for

@@ -285,7 +285,7 @@ __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __
     const int base = (blockIdx.x * kQHeadWaves + wid) * 16;
     const int ia = min(base + c, n - 1);                 // this lane's agent (clamped: junk rows, never written)
     const int row = rm.rows ? rm.rows[ia] : ia;
-    const int env = rm.rows ? row / rm.rowcap : ia;
+    const int env = rm.rows ? (rm.prob_by_row ? row : row / rm.rowcap) : ia;     // the prob row
     // ---- Dense-Obs^T [256 x 16]: the conv activations of this lane's agent, 4 consecutive per chunk step
     f32x4 hobs[16];
     if constexpr (kImg) {
@@ -676,6 +676,19 @@ MFX_API int mfx_qnet_act_rollout(void* handle, const float* d_view, const float*
                     rm, E * rowcap, nullptr, d_act, st, d_total);
 }
 
+// mfx_qnet_act_rollout with a mean action per agent (the neighbourhood mean): row e * rowcap + j reads
+// d_prob_rows [E][rowcap][A] float32 at its own index where the call above reads the env's row of d_mean.
+MFX_API int mfx_qnet_act_rollout_rows(void* handle, const float* d_view, const float* d_feat, const int32_t* d_counts,
+                                      const float* d_prob_rows, int E, int G, int g, int rowcap, int32_t* d_rows,
+                                      int32_t* d_total, int32_t* d_act, void* stream) {
+    auto* q = static_cast<QNetHandle*>(handle);
+    hipStream_t st = (hipStream_t)stream;
+    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
+    QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap, 1};
+    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_prob_rows, 0, q->dev.A, rm, E * rowcap, nullptr, d_act, st,
+                    d_total);
+}
+
 // The Boltzmann acting mode (qsample.h): refused before anything is launched unless T is finite and > 0.
 static int qsample_temperature(const char* who, float T) {
     if (std::isfinite(T) && T > 0.f) return 0;
@@ -709,6 +722,21 @@ MFX_API int mfx_qnet_act_rollout_sample(void* handle, const float* d_view, const
     const QSample qs{temperature, seed, step, g, nullptr};
     return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_mean + (size_t)g * mean_stride, 1, (size_t)G * mean_stride,
                     rm, E * rowcap, nullptr, d_act, st, d_total, &qs);
+}
+
+// mfx_qnet_act_rollout_sample with a mean action per agent (mfx_qnet_act_rollout_rows' d_prob_rows).
+MFX_API int mfx_qnet_act_rollout_rows_sample(void* handle, const float* d_view, const float* d_feat,
+                                             const int32_t* d_counts, const float* d_prob_rows, int E, int G, int g,
+                                             int rowcap, int32_t* d_rows, int32_t* d_total, int32_t* d_act,
+                                             float temperature, uint32_t seed, uint32_t step, void* stream) {
+    auto* q = static_cast<QNetHandle*>(handle);
+    MFX_CHECK(qsample_temperature("qnet_act_rollout_rows_sample", temperature));
+    hipStream_t st = (hipStream_t)stream;
+    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
+    QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap, 1};
+    const QSample qs{temperature, seed, step, g, nullptr};
+    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_prob_rows, 0, q->dev.A, rm, E * rowcap, nullptr, d_act, st,
+                    d_total, &qs);
 }
 
 }  // extern "C"

@@ -243,7 +243,7 @@ k_qb16_head(QB16Net p, const uint16_t* __restrict__ act, int n, const float* __r
         base[a] = ((blockIdx.x * kB16HeadWaves + wid) * kB16HeadTiles + a) * 16;
         ia[a] = min(base[a] + c, n - 1);                 // this lane's agents (clamped: junk columns, never written)
         row[a] = rm.rows ? rm.rows[ia[a]] : ia[a];
-        env[a] = rm.rows ? row[a] / rm.rowcap : ia[a];
+        env[a] = rm.rows ? (rm.prob_by_row ? row[a] : row[a] / rm.rowcap) : ia[a];     // the prob row
     }
     // ---- Dense-Obs^T [256 x 32 agents]: k-step s = conv position s; this lane's 8 activations of it: 16 B at 8 h
     f32x4 hobs[2][16];

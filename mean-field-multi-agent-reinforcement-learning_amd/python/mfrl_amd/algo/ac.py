@@ -36,6 +36,8 @@ class ActorCritic:
     # the trained blob is copied into self.net and handed to the acting forward device to device.  The two backends
     # keep separate Adam moments and step counts.
     _train_backend = "torch"
+    _mean_field = "group"       # the device rollout loops: "group" (the reference's mean), or "neighbors" 
+    _mf_radius = 6              # mean_field "neighbors": the Chebyshev radius (the Battle view's)
 
     def __init__(self, sess, name, handle, env, value_coef=0.1, ent_coef=0.08, gamma=0.95, batch_size=64,
                  learning_rate=1e-4):
@@ -67,6 +69,28 @@ class ActorCritic:
     @property
     def vars(self):
         return list(self.net.parameters())
+
+    @property
+    def mean_field(self):
+        """The mean action the model stores (its value head reads it in training) on the device rollout loops (play_rollout*, battle_rollout):
+        "group" (the default and the reference's: one mean per (env, group), the group-wide mean of the previous
+        step's one-hot actions) or "neighbors" (opt-in, DESIGN 7n: the paper's a_bar_j, one row per agent -- the mean
+        over the agents of its own group within Chebyshev distance mf_radius of it, mfrl_amd.mf.NeighborMean).
+        Mean-field models only; the host loops (play, play_batched) refuse a "neighbors" model."""
+        return self._mean_field
+
+    @mean_field.setter
+    def mean_field(self, value):
+        self._mean_field = mf.check_mean_field(self, value)
+
+    @property
+    def mf_radius(self):
+        """The radius of mean_field = "neighbors": an integer >= 0 (default 6, the Battle view's radius)."""
+        return self._mf_radius
+
+    @mf_radius.setter
+    def mf_radius(self, value):
+        self._mf_radius = mf.check_mf_radius(value)
 
     @property
     def train_backend(self):
@@ -199,11 +223,13 @@ class ActorCritic:
 
     # ---- the device rollout loop (play.play_rollout_episodes)
     @torch.no_grad()
-    def act_rollout(self, eng, group):
+    def act_rollout(self, eng, group, prob_rows=None):
         """Sampled actions of group `group` of a BattleBatch's rollout from its observation buffers into its action
         buffer (mfrl_amd.policy.ACNetHIP.act_rollout) with the current weights and the draw of act_dev (self.seed,
         the act count); nothing is read back.  The weights are uploaded on the caller's current stream: when they
-        moved and the engine sits on another stream, the engine's stream waits for the upload."""
+        moved and the engine sits on another stream, the engine's stream waits for the upload.  prob_rows (the mean
+        action per agent of mean_field = "neighbors") is accepted and not read: the policy head takes no mean action,
+        only the value head does, in training, from the collected rows."""
         if not self._hip_ok():
             raise ValueError("act_rollout: the HIP forward takes 2..32 actions, views of at most 4096 floats and at "
                              "most 256 features")

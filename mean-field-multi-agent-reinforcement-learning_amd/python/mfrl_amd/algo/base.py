@@ -41,6 +41,8 @@ class ValueNet:
     _explore = "greedy"         # act_dev / act_rollout: "greedy" (the reference's argmax), or "boltzmann" (csrc/qsample.h)
     _target_rule = "max"        # training target: "max" (the reference's rule), or "boltzmann" (the paper's v^MF)
     target_temperature = None   # target_rule "boltzmann": None = self.temperature (the last acting eps); a float overrides it
+    _mean_field = "group"       # the device rollout loops: "group" (the reference's mean), or "neighbors" 
+    _mf_radius = 6              # mean_field "neighbors": the Chebyshev radius (the Battle view's)
 
     def __init__(self, sess, env, handle, name, update_every=5, use_mf=False, learning_rate=1e-4, tau=0.005,
                  gamma=0.95):
@@ -87,6 +89,28 @@ class ValueNet:
         if value not in EXPLORE:
             raise ValueError("explore %r (one of %s)" % (value, ", ".join(EXPLORE)))
         self._explore = value
+
+    @property
+    def mean_field(self):
+        """The mean action the model acts on and stores on the device rollout loops (play_rollout*, battle_rollout):
+        "group" (the default and the reference's: one mean per (env, group), the group-wide mean of the previous
+        step's one-hot actions) or "neighbors" (opt-in, DESIGN 7n: the paper's a_bar_j, one row per agent -- the mean
+        over the agents of its own group within Chebyshev distance mf_radius of it, mfrl_amd.mf.NeighborMean).
+        Mean-field models only; the host loops (play, play_batched) refuse a "neighbors" model."""
+        return self._mean_field
+
+    @mean_field.setter
+    def mean_field(self, value):
+        self._mean_field = mf.check_mean_field(self, value)
+
+    @property
+    def mf_radius(self):
+        """The radius of mean_field = "neighbors": an integer >= 0 (default 6, the Battle view's radius)."""
+        return self._mf_radius
+
+    @mf_radius.setter
+    def mf_radius(self, value):
+        self._mf_radius = mf.check_mf_radius(value)
 
     @property
     def target_rule(self):
@@ -340,7 +364,7 @@ class ValueNet:
         return self._hip
 
     @torch.no_grad()
-    def act_rollout(self, eng, group, eps=None):
+    def act_rollout(self, eng, group, eps=None, prob_rows=None):
         """Greedy actions of group `group` of a BattleBatch's rollout from its observation buffers into its action
         buffer (mfrl_amd.policy.QNetHIP.act_rollout), with the eval net's current weights; nothing is read back.
         The weights are uploaded on the caller's current stream: when they moved and the engine sits on another
@@ -348,7 +372,10 @@ class ValueNet:
 
         explore = "boltzmann": row j of env e is drawn from softmax(q / eps) with the uniform (self.seed, the count
         of acting calls, group, e * rowcap + j); eps None: self.temperature (the last eps, 0.1 at first).  With the
-        default "greedy", eps is not used."""
+        default "greedy", eps is not used.
+
+        prob_rows (None: the rollout's group mean): the mean action per agent, float32 [E, rowcap, A] on the device
+        (mean_field = "neighbors": mfrl_amd.mf.NeighborMean.rows), handed to QNetHIP.act_rollout."""
         if not (self.view_space == (13, 13, 7) and self.num_actions <= 32):
             raise ValueError("act_rollout: the HIP forward takes the Battle view (13, 13, 7) and at most 32 actions")
         before = self._hip_key
@@ -360,9 +387,9 @@ class ValueNet:
                 self.temperature = eps
             T = check_temperature(self.temperature)
             self._draws += 1
-            hip.act_rollout(eng, group, temperature=T, seed=self.seed, step=self._draws)
+            hip.act_rollout(eng, group, temperature=T, seed=self.seed, step=self._draws, prob_rows=prob_rows)
             return
-        hip.act_rollout(eng, group)
+        hip.act_rollout(eng, group, prob_rows=prob_rows)
 
     def act(self, **kwargs):
         return self.act_dev(**kwargs).cpu().numpy().astype(np.int32)

@@ -12,6 +12,9 @@
   their episode chains (the collector's linked path) and train_rollout() trains on them in place.
 * battle_rollout: an evaluation round (battle) on the device rollout loop for any pairing of models with act_rollout,
   the outcomes of the episodes kept on the device by mfrl_amd.scoreboard.RolloutScoreboard.
+* A model whose mean_field is "neighbors" (MFQ / MFAC, opt-in) gets the paper's neighbourhood mean action on the three
+  device-loop rounds -- one row per agent from mfrl_amd.mf.NeighborMean in place of the group's mean, for acting and in
+  the collected rows; the host loops (play, play_batched) refuse such a model.
 * The three device-loop rounds take recorder=: a mfrl_amd.recorder.RolloutRecorder that records a few watched envs, to
   be re-run and rendered behind the round (mfrl_amd.recorder.replay).
 """
@@ -48,8 +51,18 @@ def _one_hot_mean(acts, n_action):
     return np.mean(list(map(lambda x: np.eye(n_action)[x], acts)), axis=0, keepdims=True)
 
 
+def _refuse_neighbors(name, models):
+    """The host loops feed every agent its group's mean (the reference's loop): a model that asks for the
+    neighbourhood mean is refused, not served the other definition quietly."""
+    for m in models:
+        if getattr(m, "mean_field", "group") != "group":
+            raise ValueError("%s: %s has mean_field %r, which only the device rollout loops (play_rollout, "
+                             "play_rollout_episodes, battle_rollout) provide" % (name, type(m).__name__, m.mean_field))
+
+
 def play(env, n_round, map_size, max_steps, handles, models, print_every, eps=1.0, render=False, train=False):
     """One round of self-play on one env (senario_battle.py:55-185)."""
+    _refuse_neighbors("play", models)
     env.reset()
     generate_map(env, map_size, handles)
     step_ct, done, n_group = 0, False, len(handles)
@@ -111,6 +124,7 @@ def play_batched(eng, n_round, map_size, max_steps, models, print_every=50, eps=
     """One round on all E envs of `eng` (a BattleBatch), device-resident end to end.
 
     Returns (max_nums, nums, mean_rewards, total_rewards) summed over envs, like play()."""
+    _refuse_neighbors("play_batched", models)
     E, G = eng.n_envs, 2
     eng.reset()
     left, right = block_positions(map_size)
@@ -262,17 +276,34 @@ def play_rollout_episodes(eng, n_round, map_size, max_steps, models, print_every
                           lambda: models[0].rollout_collector(eng, 0), models[0].train_rollout, recorder)
 
 
-def _act_rollout(model, eng, g, eps):
+def _act_rollout(model, eng, g, eps, nm=None):
     """model.act_rollout for one group of a device-loop round: a model that explores (ValueNet.explore other than
     "greedy") gets the round's eps as its temperature; every other model is called as it always was.  A model that
     trains on the Boltzmann target (ValueNet.target_rule) records the round's eps even while it acts greedily, as
-    act_dev records it: its training reads model.temperature."""
+    act_dev records it: its training reads model.temperature.  nm: the group's NeighborMean when the model's
+    mean_field is "neighbors" (its rows are the mean action per agent), else None: exactly the calls above."""
     if getattr(model, "target_rule", "max") != "max":
         model.temperature = eps
+    kw = {"prob_rows": nm.rows} if nm is not None else {}
     if getattr(model, "explore", "greedy") != "greedy":
-        model.act_rollout(eng, g, eps=eps)
+        model.act_rollout(eng, g, eps=eps, **kw)
     else:
-        model.act_rollout(eng, g)
+        model.act_rollout(eng, g, **kw)
+
+
+def _neighbor_means(eng, models, G=2):
+    """Per group: the mfrl_amd.mf.NeighborMean of a model whose mean_field is "neighbors" (made once and kept on the
+    model while the engine's layout, the group and the radius stay the same), None for a model left at "group".
+    Call it behind rollout_init: the rows have the rollout's rowcap."""
+    out = [None] * G
+    for g, m in enumerate(models[:G]):
+        if getattr(m, "mean_field", "group") != "neighbors":
+            continue
+        kept = m.__dict__.setdefault("_neighbor_means", {})
+        if g not in kept or not kept[g].matches(eng, g, m.mf_radius):
+            kept[g] = mf.NeighborMean(eng, g, m.mf_radius)
+        out[g] = kept[g]
+    return out
 
 
 def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, left_id, collector, train_fn,
@@ -290,7 +321,13 @@ def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, 
     if eng.rollout_policy_path() is None:
         raise RuntimeError("%s: this rollout plan takes no learned policy (MFX_ROLLOUT_PIPE=1)" % name)
     eng.rollout_policy_observe()
+    nms = _neighbor_means(eng, models, G)
+    for nm in nms:
+        if nm is not None:
+            nm.reset()
     col = collector() if train else None
+    if col is not None:
+        col.prob_rows = nms[0].rows if nms[0] is not None else None
     if recorder is not None:
         recorder.attach(map_size, max_steps, placement)
     max_nums = [len(placement[g]) * E for g in range(G)]
@@ -298,12 +335,15 @@ def _rollout_round(name, eng, n_round, map_size, max_steps, models, eps, train, 
     t_play = time.time()
     for step_ct in range(max_steps):
         for g in range(G):
-            _act_rollout(models[g], eng, g, eps)
+            _act_rollout(models[g], eng, g, eps, nms[g])
         if col is not None:
             col.begin()
         eng.rollout_policy_step()
         if col is not None:
             col.end()
+        for nm in nms:                      # behind col.end(): the rows collected are those the policy acted with
+            if nm is not None:
+                nm.update()
         if recorder is not None:
             recorder.update()
     rows = col.finish() if col is not None else 0
@@ -373,6 +413,10 @@ def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, ep
     if eng.rollout_policy_path() is None:
         raise RuntimeError("battle_rollout: this rollout plan takes no learned policy (MFX_ROLLOUT_PIPE=1)")
     eng.rollout_policy_observe()
+    nms = _neighbor_means(eng, models, G)
+    for nm in nms:
+        if nm is not None:
+            nm.reset()
     if board is None:
         board = RolloutScoreboard(eng)
     board.attach()
@@ -384,8 +428,11 @@ def battle_rollout(eng, n_round, map_size, max_steps, models, print_every=50, ep
     step_ct = 0
     while step_ct < max_steps:
         for g in range(G):
-            _act_rollout(models[g], eng, g, eps)
+            _act_rollout(models[g], eng, g, eps, nms[g])
         eng.rollout_policy_step()
+        for nm in nms:
+            if nm is not None:
+                nm.update()
         board.update()
         if recorder is not None:
             recorder.update()

@@ -56,9 +56,25 @@ def main(argv=None):
                              "(drawn from softmax(q / --temperature))")
     parser.add_argument("--temperature", type=float, default=None,
                         help="with --explore boltzmann: the temperature, finite and > 0 (default 0.1)")
+    parser.add_argument("--mean_field", type=str, choices=["group", "neighbors"], default="group",
+                        help="with --envs > 1: the mean action the mean-field models (mfq / mfac) of the pairing are given "
+                             "-- group (the reference) or neighbors (the agents of the group within --mf_radius cells)")
+    parser.add_argument("--mf_radius", type=int, default=None,
+                        help="with --mean_field neighbors: the Chebyshev radius, >= 0 (default 6, the view's)")
     args = parser.parse_args(argv)
     if args.oppo is None:
         args.oppo = args.algo
+    if args.mean_field != "group":
+        if args.algo not in ("mfq", "mfac") and args.oppo not in ("mfq", "mfac"):
+            parser.error("--mean_field neighbors is the mean action of a mean-field model: neither --algo nor --oppo is "
+                         "mfq or mfac")
+        if args.envs <= 1:
+            parser.error("--mean_field neighbors runs on the device rollout loop: --envs > 1")
+    if args.mf_radius is not None:
+        if args.mean_field == "group":
+            parser.error("--mf_radius is the radius of --mean_field neighbors: give that too")
+        if args.mf_radius < 0:
+            parser.error("--mf_radius must be >= 0")
     if args.explore != "greedy" and args.algo not in ("mfq", "il") and args.oppo not in ("mfq", "il"):
         parser.error("--explore boltzmann samples from the Q values: neither --algo nor --oppo is mfq or il")
     if args.temperature is not None and args.explore == "greedy":
@@ -114,6 +130,10 @@ def main(argv=None):
     for m in models:
         if args.explore != "greedy" and hasattr(type(m), "explore"):     # (the Q models of the pairing)
             m.explore = args.explore
+        if args.mean_field != "group" and getattr(m, "use_mf", getattr(m, "_use_mf", False)):   # (the mean-field models)
+            m.mean_field = args.mean_field
+            if args.mf_radius is not None:
+                m.mf_radius = args.mf_radius
     win_cnt = {"main": 0, "opponent": 0}
     t0 = time.time()
     if args.envs == 1:

@@ -5,6 +5,8 @@
     mfac_returns(rewards, offsets, values, g) algo/ac.py:305-320 (discounted returns, float64 running
                                              return stored as float32: the reference's NumPy-1 rules)
     mfq_target_boltzmann(e_q, t_q, r, d, g, T)  the opt-in Boltzmann value target (the paper's v^MF), float64
+    neighbor_mean(pos, actions, counts, ..)  the opt-in neighbourhood mean action (the paper's a_bar_j), float32
+    NeighborMean(eng, group, radius)         the same per step of the device rollout loop, one row per agent
     q_sample(q, temperature, seed, step)     the Boltzmann draw over Q rows (csrc/qsample.h): the opt-in exploration
                                              of the Q models; no counterpart in the reference, whose act is greedy
 """
@@ -46,6 +48,92 @@ def mean_action(actions, counts, n_action):
     check(L.mfx_mean_action(_p(actions.contiguous()), _p(counts.contiguous()), B, rowcap, n_action, _p(out),
                             _stream()), "mfx_mean_action")
     return out
+
+
+MEAN_FIELDS = ("group", "neighbors")     # ValueNet.mean_field / ActorCritic.mean_field
+
+
+def check_mean_field(model, value):
+    """The mean_field setter of the models: "group" (the reference's group-wide mean) or "neighbors" (the opt-in
+    neighbourhood mean, NeighborMean), the latter only on a mean-field model."""
+    if value not in MEAN_FIELDS:
+        raise ValueError("mean_field %r (one of %s)" % (value, ", ".join(MEAN_FIELDS)))
+    if value != "group" and not getattr(model, "use_mf", getattr(model, "_use_mf", False)):
+        raise ValueError("mean_field %r needs a mean-field model (MFQ / MFAC); %s reads no mean action"
+                         % (value, type(model).__name__))
+    return value
+
+
+def check_mf_radius(value):
+    """The mf_radius setter of the models: an int >= 0."""
+    if isinstance(value, bool) or int(value) != value or int(value) < 0:
+        raise ValueError("mf_radius must be an integer >= 0, got %r" % (value,))
+    return int(value)
+
+
+def neighbor_mean(pos, actions, counts, n_action, radius, map_w, map_h, out=None):
+    """The neighbourhood mean action on compact lists (k_neighbor_mean; the contract of include/magent_amd.h part 4b,
+    restated in tests/neighbor_mean_ref.py): pos int32 [B, rowcap, 2] (x, y), actions int32 [B, rowcap], counts int32
+    [B] -> float32 [B, rowcap, n_action]; row j < counts[b] is the mean of the one-hot actions of list b's members
+    within Chebyshev distance `radius` of member j, itself included, (float)(count / n) computed in float64.  An
+    action outside [0, n_action) is counted in no entry while the divisor stays.  Rows at and past the count are left
+    as they are (out: the tensor to write into; None: a new one of zeros).  The positions of a list must be distinct
+    cells inside the map (not checked).  Any other dtype raises TypeError; 1 <= n_action <= 64, radius >= 0 and a map
+    that fits the LDS grid (256 x 256 does, 512 x 512 does not) are the library's refusals."""
+    _dtype("neighbor_mean", pos=(pos, torch.int32), actions=(actions, torch.int32), counts=(counts, torch.int32))
+    if actions.dim() != 2 or pos.shape != tuple(actions.shape) + (2,) or counts.shape != (actions.shape[0],):
+        raise ValueError("neighbor_mean: pos %s, actions %s, counts %s" % tuple(
+            tuple(x.shape) for x in (pos, actions, counts)))
+    B, rowcap = actions.shape
+    if out is None:
+        out = torch.zeros((B, rowcap, max(int(n_action), 0)), dtype=torch.float32, device=actions.device)
+    else:
+        _dtype("neighbor_mean", out=(out, torch.float32))
+        if out.shape != (B, rowcap, n_action) or not out.is_contiguous():
+            raise ValueError("neighbor_mean: out of shape %s for [%d, %d, %d]" % (tuple(out.shape), B, rowcap, n_action))
+    L = lib()
+    L.mfx_neighbor_mean.restype = ctypes.c_int
+    check(L.mfx_neighbor_mean(_p(pos.contiguous()), _p(actions.contiguous()), _p(counts.contiguous()), B, rowcap,
+                              int(n_action), int(radius), int(map_w), int(map_h), _p(out), _stream()),
+          "mfx_neighbor_mean")
+    return out
+
+
+class NeighborMean:
+    """The neighbourhood mean action of group `group` of a BattleBatch on the device rollout loop (opt-in):
+
+        eng.rollout_policy_observe();  nm.reset()
+        per step:  model.act_rollout(eng, group, prob_rows=nm.rows) ... eng.rollout_policy_step();  nm.update()
+
+    rows: float32 CUDA tensor [E, rowcap, n_action]; after update(), row j < group_num[e] of env e is the mean of the
+    one-hot actions the step consumed over the survivors of the group within Chebyshev distance `radius` of survivor
+    j (itself included; agents that died in the step count for nobody), and all zero when the env restarted in the
+    step or after reset().  Rows at and past group_num keep what they held.  One launch per call on the engine's
+    stream; the carried state (the group sizes and episode numbers of the previous call) lives on the device and
+    nothing is read back.  Needs minimap_mode (the position comes from the feature row) and rollout_init."""
+
+    def __init__(self, eng, group, radius):
+        self.eng, self.group, self.radius = eng, int(group), check_mf_radius(radius)
+        self.n_action = int(eng.env.get_action_space(eng.handles[self.group])[0])
+        L = eng._dll
+        L.mfx_neighbor_mean_reset.restype = ctypes.c_int
+        L.mfx_neighbor_mean_rollout.restype = ctypes.c_int
+        with torch.cuda.stream(eng.torch_stream()):
+            self.rows = torch.zeros((eng.n_envs, eng.rowcap, self.n_action), dtype=torch.float32, device="cuda")
+            self._state = torch.zeros(2 * eng.n_envs, dtype=torch.int32, device="cuda")
+
+    def matches(self, eng, group, radius):
+        """Whether this object serves (eng, group, radius) as the engine is laid out now."""
+        return (self.eng is eng and self.group == int(group) and self.radius == int(radius)
+                and self.rows.shape[:2] == (eng.n_envs, eng.rowcap))
+
+    def reset(self):
+        self.eng._check(self.eng._dll.mfx_neighbor_mean_reset(self.eng.game, self.group, _p(self.rows), _p(self._state)),
+                        "neighbor_mean_reset")
+
+    def update(self):
+        self.eng._check(self.eng._dll.mfx_neighbor_mean_rollout(self.eng.game, self.group, self.radius, _p(self.rows),
+                                                                _p(self._state)), "neighbor_mean_rollout")
 
 
 def mfq_target(e_q, t_q, rewards, dones, gamma=0.95):

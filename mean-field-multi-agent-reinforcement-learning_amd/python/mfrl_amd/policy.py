@@ -166,7 +166,8 @@ class QNetHIP:
         for fn in ("mfx_qnet_create", "mfx_qnet_destroy", "mfx_qnet_set_weights", "mfx_qnet_forward",
                    "mfx_qnet_act_rollout", "mfx_qnet_set_precision", "mfx_qnet_precision"):
             getattr(L, fn).restype = ctypes.c_int
-        for fn in ("mfx_qnet_forward_sample", "mfx_qnet_act_rollout_sample"):    # (absent from older builds, which
+        for fn in ("mfx_qnet_forward_sample", "mfx_qnet_act_rollout_sample",     # (absent from older builds, which
+                   "mfx_qnet_act_rollout_rows", "mfx_qnet_act_rollout_rows_sample"):
             if hasattr(L, fn):                                                   #  the bench scripts may load)
                 getattr(L, fn).restype = ctypes.c_int
         self._L = L
@@ -228,11 +229,14 @@ class QNetHIP:
     def act(self, view, feature, prob=None, temperature=None, seed=0, step=0):
         return self.forward(view, feature, prob, want_q=False, temperature=temperature, seed=seed, step=step)[1]
 
-    def act_rollout(self, eng, group, temperature=None, seed=0, step=0):
+    def act_rollout(self, eng, group, temperature=None, seed=0, step=0, prob_rows=None):
         """Actions of group `group` of a BattleBatch rollout from its current observation buffers and
         former mean actions, written into the rollout's action buffer [E][G][rowcap] (live rows only).
         temperature (None: greedy): the Boltzmann draw of forward(), row j of env e with the uniform
         (seed, step, group, e * rowcap + j).
+        prob_rows (None: the rollout's mean action of the env, one row per (env, group)): a float32 CUDA tensor
+        [E, rowcap, A], contiguous -- row j of env e reads its own mean action prob_rows[e, j] (the neighbourhood mean,
+        mfrl_amd.mf.NeighborMean.rows); it must be ready on the engine's stream.
 
         Works on every plan that takes a learned policy (BattleBatch.rollout_policy_path: all but
         MFX_ROLLOUT_PIPE=1 -- large batches, large envs and few-env batches alike; E, rowcap and the buffers come
@@ -247,6 +251,20 @@ class QNetHIP:
             eng._check(eng._dll.mfx_battle_rollout_buffer(eng.game, name.encode(), group if name in ("view", "feature")
                                                           else 0, ctypes.byref(p), ctypes.byref(nb)), "rollout_buffer")
             ptr[name] = p
+        if prob_rows is not None:
+            if (prob_rows.dtype != torch.float32 or not prob_rows.is_cuda or not prob_rows.is_contiguous()
+                    or tuple(prob_rows.shape) != (E, rc, self.A)):
+                raise ValueError("QNetHIP.act_rollout: prob_rows must be a contiguous float32 CUDA tensor [%d, %d, %d], "
+                                 "got %s %s" % (E, rc, self.A, prob_rows.dtype, tuple(prob_rows.shape)))
+            args = (self.handle, ptr["view"], ptr["feature"], ptr["group_num"], _ptr(prob_rows), int(E), int(G),
+                    int(group), int(rc), _P(self._rows.data_ptr()), _P(self._rows.data_ptr() + 4 * E * rc), ptr["actions"])
+            if temperature is not None:
+                check(self._L.mfx_qnet_act_rollout_rows_sample(
+                    *args, ctypes.c_float(temperature), ctypes.c_uint32(seed & 0xFFFFFFFF),
+                    ctypes.c_uint32(step & 0xFFFFFFFF), _P(eng.stream_handle())), "mfx_qnet_act_rollout_rows_sample")
+            else:
+                check(self._L.mfx_qnet_act_rollout_rows(*args, _P(eng.stream_handle())), "mfx_qnet_act_rollout_rows")
+            return
         stride = eng.mean_stride()
         if temperature is not None:
             check(self._L.mfx_qnet_act_rollout_sample(

@@ -111,10 +111,16 @@ class RolloutCollector:
     row of the same agent's previous step in the same episode, or -1) and tail (the row is its agent's last so far)
     through a device table of the newest row per (env, id), which the session's first begin() resets.  An agent's
     chain so ends at its death, at the end of its episode (done or the step cap), or at the end of the session.
-    The linked path refuses rows pushed by other means (they have no links): ValueError at begin()."""
+    The linked path refuses rows pushed by other means (they have no links): ValueError at begin().
 
-    def __init__(self, eng, memory_group, group=0, capacity=None):
+    prob_rows (None: the prob column is the env's mean action, the rollout's mean buffer cast to float): a float32 CUDA
+    tensor [E, rowcap, n_action], contiguous -- the row of agent j of env e takes prob_rows[e, j] bit for bit (the
+    neighbourhood mean, mfrl_amd.mf.NeighborMean.rows).  begin() reads it on the engine's stream: it must hold what
+    the policy acted with.  end, end_linked and finish are the same on both paths."""
+
+    def __init__(self, eng, memory_group, group=0, capacity=None, prob_rows=None):
         self.eng, self.mg, self.group, self.capacity = eng, memory_group, int(group), capacity
+        self.prob_rows = prob_rows          # see the class docstring; may be set between steps
         self._bound = None                  # upper bound of the device row counter; None: no step since finish()
         self._state = self._scratch = self._last = None
         self._src = self._dst = None
@@ -125,6 +131,8 @@ class RolloutCollector:
             for fn in ("mfx_collect_reset", "mfx_collect_begin", "mfx_collect_end", "mfx_collect_end_linked",
                        "mfx_collect_links_reset"):
                 getattr(L, fn).restype = ctypes.c_int
+            if hasattr(L, "mfx_collect_begin_rows"):        # (absent from older builds, which the bench scripts may load)
+                L.mfx_collect_begin_rows.restype = ctypes.c_int
             self._L = L
 
     @property
@@ -207,6 +215,17 @@ class RolloutCollector:
                         ctypes.c_void_p(c["tail"].data_ptr())) if self.linked else None)
         self._ptrs = (ctypes.c_void_p(self._scratch.data_ptr()), ctypes.c_void_p(self._scratch.data_ptr() + 4 * E * rc),
                       ctypes.c_void_p(self._state.data_ptr()))
+        P = self.prob_rows
+        if P is not None:
+            if not rows.use_mean:
+                raise ValueError("RolloutCollector: prob_rows given, but the step rows have no prob column")
+            if (P.dtype != torch.float32 or not P.is_cuda or not P.is_contiguous()
+                    or tuple(P.shape) != (E, rc, int(rows.act_n))):
+                raise ValueError("RolloutCollector: prob_rows must be a contiguous float32 CUDA tensor [%d, %d, %d], got "
+                                 "%s %s" % (E, rc, int(rows.act_n), P.dtype, tuple(P.shape)))
+            check(self._L.mfx_collect_begin_rows(ctypes.byref(self._src), ctypes.byref(self._dst),
+                                                 ctypes.c_void_p(P.data_ptr()), *self._ptrs, st), "mfx_collect_begin_rows")
+            return
         check(self._L.mfx_collect_begin(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs, st),
               "mfx_collect_begin")
 

@@ -9,6 +9,7 @@
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --render --watch 0 63 ...   # + frames of two envs
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann ...   # sample from softmax(q / eps)
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann --target boltzmann ...   # + the paper's v^MF target
+    python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --mean_field neighbors --mf_radius 6 ...   # the paper's neighbourhood mean action
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -76,7 +77,25 @@ def main(argv=None):
                         help="mfq / il: what training bootstraps from -- max (the reference: the target net's value of the "
                              "greedy next action) or boltzmann (the paper's mean-field value: the target net's values "
                              "averaged under softmax(q / eps), eps from the schedule); either --train_backend")
+    parser.add_argument("--mean_field", type=str, choices=["group", "neighbors"], default="group",
+                        help="mfq / mfac with --rollout / --rollout_episodes: the mean action an agent is given -- group "
+                             "(the reference: the mean over its whole group) or neighbors (the paper's: the mean over "
+                             "the agents of its group within --mf_radius cells of it)")
+    parser.add_argument("--mf_radius", type=int, default=None,
+                        help="with --mean_field neighbors: the Chebyshev radius, >= 0 (default 6, the view's)")
     args = parser.parse_args(argv)
+    if args.mean_field != "group":
+        if args.algo not in ("mfq", "mfac"):
+            parser.error("--mean_field neighbors is the mean action of a mean-field model: --algo mfq or mfac (ac / il "
+                         "read no mean action)")
+        if not (args.rollout or args.rollout_episodes):
+            parser.error("--mean_field neighbors runs on the device rollout loops: --rollout (mfq) or --rollout_episodes "
+                         "(mfac)")
+    if args.mf_radius is not None:
+        if args.mean_field == "group":
+            parser.error("--mf_radius is the radius of --mean_field neighbors: give that too")
+        if args.mf_radius < 0:
+            parser.error("--mf_radius must be >= 0")
     if args.target != "max" and args.algo not in ("mfq", "il"):
         parser.error("--target boltzmann bootstraps from the Q values: --algo mfq or il (ac / mfac train on their "
                      "returns)")
@@ -135,6 +154,10 @@ def main(argv=None):
             m.explore = args.explore
         if args.target != "max":
             m.target_rule = args.target
+        if args.mean_field != "group":
+            m.mean_field = args.mean_field
+            if args.mf_radius is not None:
+                m.mf_radius = args.mf_radius
     play_handle = play
     if args.envs > 1:
         from .battle import BattleBatch
