@@ -321,6 +321,14 @@ int mfx_qnet_set_weights(void *handle, const float *d_blob, size_t n_floats, voi
  * `stream`, so switching needs no re-upload and the f32 results are the same before and after. */
 int mfx_qnet_set_precision(void *handle, int precision, void *stream);
 int mfx_qnet_precision(void *handle, int *precision);
+/* A forward needs weights.  Every acting call of this part -- mfx_qnet_forward, mfx_qnet_act_rollout and their
+ * _sample / _rows forms, mfx_acnet_forward, mfx_acnet_act_rollout -- on a handle that has had no mfx_*_set_weights
+ * returns -1 ("... needs weights (mfx_*_set_weights)" in mfx_last_error()) in both precisions, before anything is
+ * launched: until then the blob and the weight images the kernels read are bare allocations.  One handle may serve
+ * callers on several streams (two engines that share a network): the Q network's pass buffer is kept per stream, and
+ * each caller brings its own d_rows / d_total.  Each stream that ever calls a Q handle keeps its buffer, grow-only
+ * (10 KB per row of its largest call, at most 2^18 rows = 2.7 GB), until mfx_qnet_destroy; and the calls on one handle
+ * must come from one host thread at a time (the per-stream table, like the rest of the handle, is not locked). */
 /* n agents: view [n][1183], feature [n][F], prob [n][A] (mean field, else null) -> q [n][A], act [n] */
 int mfx_qnet_forward(void *handle, const float *d_view, const float *d_feat, const float *d_prob, int n, float *d_q,
                      int32_t *d_act, void *stream);
@@ -416,7 +424,8 @@ int mfx_acnet_input_support_size(void *handle, int *k);
 int mfx_acnet_set_precision(void *handle, int precision, void *stream);
 int mfx_acnet_precision(void *handle, int *precision);
 /* n agents: view [n][view_floats], feature [n][F], prob [n][A] float32 (the MF value head; else null) ->
- * policy [n][A], value [n], act [n] (each may be null); row i drawn with (seed, step, group 0, row i) */
+ * policy [n][A], value [n], act [n] (each may be null); row i drawn with (seed, step, group 0, row i).  Needs weights
+ * (the rule at mfx_qnet_forward). */
 int mfx_acnet_forward(void *handle, const float *d_view, const float *d_feat, const float *d_prob, int n,
                       float *d_policy, float *d_value, int32_t *d_act, uint32_t seed, uint32_t step, void *stream);
 /* group g of a rollout batch -> sampled actions in the rollout's action buffer (live rows; row j of env e drawn

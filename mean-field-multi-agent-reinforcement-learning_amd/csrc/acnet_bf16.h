@@ -1,6 +1,6 @@
 // acnet_bf16.h -- the interface between the actor-critic network's handle (acnet_kernels.hip: the C ABI, the packed
 // f32 blob) and its bf16 acting forward (acnet_bf16_kernels.hip), the weight-image geometry both sides and the tests
-// read, and the pieces the two forwards share word for word: x / 0.1 and the draw's uniform.
+// read, and x / 0.1, which the two forwards share (the row map, the uniform and this forward's epilogue: policy_act.h).
 //
 // As in qnet_bf16.h every matrix is used TRANSPOSED, as the A operand of v_mfma_f32_16x16x32_bf16 (rows = output
 // units), the layer input as the B operand (columns = agents): lane l (h = l >> 4, c = l & 15) holds A[c][8 h + j],
@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "policy_gemm.h"
+#include "policy_act.h"
 
 namespace mfx {
 
@@ -33,18 +33,6 @@ __device__ __forceinline__ float div_tenth(float x) {
     float y = __builtin_fmaf(r, 10.0f, q);
     if (__builtin_expect(x != 0.f && __builtin_fabsf(x) < 0x1p-100f, 0)) y = x / 0.1f;
     return y;
-}
-
-__device__ __forceinline__ uint32_t ac_mix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
-// The uniform of row `row` of group g at step `step` (tests/acnet_ref.py restates it).
-__device__ __forceinline__ float ac_uniform(uint32_t seed, uint32_t step, int g, int row) {
-    const uint32_t k = seed ^ ac_mix32(step * 0x9E3779B9u + (uint32_t)g * 0x632BE5ABu) ^
-                       ac_mix32((uint32_t)row * 0x85EBCA77u + 0x165667B1u);
-    return (float)(ac_mix32(k) >> 8) * (1.0f / 16777216.0f);
 }
 
 __host__ __device__ constexpr int acb16_k(bool linear, int s, int h, int j) {
@@ -79,7 +67,7 @@ struct ACB16Net {
 hipError_t acb16_build(ACB16Net* net, const float* const* w, int V, int F, int A, uint4* img, hipStream_t st);
 
 // The policy path of n rows (d_n: the count on the device, n its upper bound): policy_out [n][A] and / or the drawn
-// actions, with k_acnet's row map, slots and draw.
+// actions, by k_acnet's rule (policy_act.h ac_epilogue).
 hipError_t acb16_forward(const ACB16Net& net, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
                          QRowMap rm, int n, const int32_t* d_n, float* policy_out, int32_t* act_out, uint32_t seed,
                          uint32_t step, int group, hipStream_t st);

@@ -16,7 +16,8 @@
 //       - h_view and h_emb after bias and ReLU;
 //       - div_tenth(relu(d)): the f32 division k_acnet does (correctly rounded), then ONE rounding to bf16.
 //   * Products are accumulated in f32 (the MFMA accumulator, which starts at the f32 bias); ReLU is applied in f32.
-//   * Softmax, the clip and the draw are f32 and unrounded; the draw is ac_uniform and k_acnet's running-sum rule.
+//   * Softmax, the clip and the draw are f32 and unrounded: policy_act.h's ac_epilogue, the rule k_acnet writes out
+//     (ac_uniform and the running-sum pick).
 //   * An agent's result does not depend on its position in the batch or on the batch size: every agent is one
 //     column of its MFMAs, accumulated in one fixed order.
 //   * The view layer runs the dense k order whether or not an input support is set on the handle.
@@ -56,6 +57,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kLead = 3;                                 // chunks (and view k-steps) in flight ahead of the MFMAs
 constexpr int kMaxA = kAB16PolMT * 16;                   // policy columns
+static_assert(kMaxA == kActMaxA, "ac_epilogue's row");
 constexpr int kLgOff = 2 * kAB16Chunk;                   // (16-B units) the logits follow the two chunk buffers
 // The dynamic LDS of k_acb16: the one size the kernel's offsets and the launch share.
 constexpr size_t kAcb16Smem = (size_t)kLgOff * 16 + (size_t)kAB16Waves * 16 * kMaxA * 4;
@@ -181,7 +183,7 @@ k_acb16(ACB16Net p, const float* __restrict__ view, size_t view_ld, const float*
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, h = lane >> 4, c = lane & 15;
     const int base = (blockIdx.x * kAB16Waves + wid) * 16;
     const int ia = min(base + c, n - 1);                           // this lane's agent (clamped: junk, never written)
-    const int row = rm.rows ? rm.rows[ia] : ia;
+    const int row = rm.row(ia);
     const float* vrow = view + (size_t)row * view_ld;
     const float* vr = vrow + 8 * h;                                // this lane's 8 floats of k-step s: vr[32 s ..]
     const float* fr = feat + (size_t)row * feat_ld;
@@ -275,7 +277,7 @@ k_acb16(ACB16Net p, const float* __restrict__ view, size_t view_ld, const float*
         }
     });
     // ---- policy: logits of agent c, actions 16 t + 4 h + r, through LDS to lane c of the wave (h == 0): softmax,
-    // clip, the draw -- k_acnet's epilogue (the bias is already in the logits)
+    // clip, the draw -- ac_epilogue (the bias is already in the logits)
     float* lg = reinterpret_cast<float*>(csm + kLgOff) + wid * 16 * kMaxA;
 #pragma unroll
     for (int t = 0; t < kAB16PolMT; ++t)
@@ -285,39 +287,7 @@ k_acb16(ACB16Net p, const float* __restrict__ view, size_t view_ld, const float*
     const int i = base + c;
     if (h == 0 && i < n) {
         const int A = p.A;
-        float x[kMaxA];
-        float m = -__builtin_huge_valf();
-#pragma unroll
-        for (int a = 0; a < kMaxA; ++a) {
-            x[a] = a < A ? lg[c * kMaxA + a] : 0.f;
-            if (a < A) m = fmaxf(m, x[a]);
-        }
-        float sum = 0.f;
-#pragma unroll
-        for (int a = 0; a < kMaxA; ++a)
-            if (a < A) { x[a] = expf(x[a] - m); sum += x[a]; }
-        float tot = 0.f;
-#pragma unroll
-        for (int a = 0; a < kMaxA; ++a)
-            if (a < A) { x[a] = fminf(fmaxf(x[a] / sum, 1e-10f), 1.0f - 1e-10f); tot += x[a]; }
-        if (policy_out) {
-            float* po = policy_out + (size_t)i * A;
-            for (int a = 0; a < A; ++a) po[a] = x[a];
-        }
-        if (act_out) {
-            const float thr = ac_uniform(seed, step, group, row) * tot;
-            float run = 0.f;
-            int pick = -1;
-#pragma unroll
-            for (int a = 0; a < kMaxA; ++a)
-                if (a < A) {
-                    run += x[a];
-                    if (pick < 0 && run > thr) pick = a;
-                }
-            if (pick < 0) pick = A - 1;                             // (rounding: u * tot at the very top)
-            const size_t slot = rm.rows ? (size_t)(row / rm.rowcap) * rm.act_env + rm.act_off + row % rm.rowcap : (size_t)i;
-            act_out[slot] = pick;
-        }
+        ac_epilogue([&](int a) { return lg[c * kMaxA + a]; }, A, i, row, rm, policy_out, act_out, seed, step, group);
     }
 }
 

@@ -20,7 +20,9 @@
 // The draw: the reference samples tf.multinomial(log(policy)), i.e. action a with probability policy[a] /
 // sum(policy).  Here u = a counter hash of (seed, step, group, row) -> [0, 1) (24 bits), and the action is the
 // first a whose running f32 sum of policy[0..a] exceeds u * sum(policy) (the sums in action order) -- a pure
-// function of the policy row and the counters, restated on the host by tests/acnet_ref.py.
+// function of the policy row and the counters, restated on the host by tests/acnet_ref.py.  The uniform
+// (ac_uniform) and the row map (QRowMap) are policy_act.h's; softmax, clip and the running-sum pick are written out
+// below, the same rule as policy_act.h's ac_epilogue, which the bf16 forward calls (see the epilogue's comment).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -37,7 +39,7 @@
 namespace mfx {
 
 constexpr int kAH = 256;                 // hidden width (hidden_size[0])
-constexpr int kAMaxA = 32;               // policy columns (n_action padded)
+constexpr int kAMaxA = kActMaxA;         // policy columns (n_action padded)
 constexpr int kAMaxV = 4096;             // flattened view floats the kernel takes
 constexpr int kABlocks = 19;
 
@@ -72,11 +74,11 @@ struct ACNetDev {
     int vK;
 };
 
-// (div_tenth -- x / 0.1f, correctly rounded -- and ac_uniform, the draw's uniform: acnet_bf16.h, shared with the bf16
+// (div_tenth -- x / 0.1f, correctly rounded: acnet_bf16.h; ac_uniform and QRowMap: policy_act.h -- shared with the bf16
 // forward)
-// rows (rm.rows): compact agent i -> view / feature row; the action slot as in QRowMap; the prob row of
-// the env (mean field).  d_n: the row count on the device (launch sized for n).  policy_out [n][A],
-// value_out [n], act_out: any may be null.
+// rows (rm.rows): compact agent i -> view / feature row; the action slot as in QRowMap; the prob row of the env (the
+// MF value head: this network never takes a mean action per agent, QRowMap::prob_by_row).
+// d_n: the row count on the device (launch sized for n).  policy_out [n][A], value_out [n], act_out: any may be null.
 // kHeLds (features of at most kHeF floats, the Battle shape's 34): h_emb is never held.  Its weights sit in LDS for
 // the whole kernel and each 16-unit tile of it is recomputed from the features (9 MFMAs, 9 feature registers) right
 // where the concat needs it -- 3 % more MFMA work for 64 fewer registers per lane, which is what lets two
@@ -85,21 +87,19 @@ constexpr int kHeF = 36;
 #ifndef MFX_ACNET_SKIP
 #define MFX_ACNET_SKIP 0      // A/B builds only (make variant): 1 view layer, 2 dense layers, 4 policy layer, 8 h_emb skipped
 #endif
-constexpr size_t kAcnetLdsSmem = kQHeadSmem + (size_t)kHeF * kAH * 4;
-// The imaged forms: the two chunk buffers, We (unused space when h_emb is held: that form is one workgroup per CU
-// either way), then the view ring at kAcnetRingOff floats.
+// The dynamic LDS of k_acnet, the one size the kernel's offsets and the launch share: the two chunk buffers, We
+// (unused space when h_emb is held: that form is one workgroup per CU either way), then the view ring at
+// kAcnetRingOff floats.
 constexpr int kAcnetRingOff = 2 * kImgBuf + kHeF * kAH, kAcnetRing = 3 * 1024;
-constexpr size_t kAcnetImgLdsSmem = (size_t)(kAcnetRingOff + kAcnetRing) * 4;            // 80 KB
-// The dynamic LDS of k_acnet<.., kHeLds, kImg>: the one size the kernel's offsets and the launch share.
-constexpr size_t acnet_smem(bool he_lds, bool img) { return img ? kAcnetImgLdsSmem : he_lds ? kAcnetLdsSmem : kQHeadSmem; }
-static_assert(kAcnetImgLdsSmem >= kQHeadSmem, "the imaged form with h_emb held stages We through wg_gemm_t");
+constexpr size_t kAcnetSmem = (size_t)(kAcnetRingOff + kAcnetRing) * 4;                  // 80 KB
+static_assert(kAcnetSmem >= kQStageSmem, "the form with h_emb held stages We through wg_gemm_t");
 
-// kImg: the layers run wg_gemm_i over the weight images (direct-to-LDS staging; made by set_weights), else
-// wg_gemm_t.  GEMM<MT, NCH, kZero>(block, image, K, v_at, acc) picks the form.
-template <typename PT, bool kMF, bool kHeLds, bool kImg, bool kPack = false>
+// The layers run wg_gemm_i over the weight images (direct-to-LDS staging; made by set_weights, without which
+// acnet_run refuses the call); the wide-feature h_emb stages its weights through wg_gemm_t.
+template <bool kMF, bool kHeLds, bool kPack = false>
 __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const float* __restrict__ view, size_t view_ld,
                                                   const float* __restrict__ feat, size_t feat_ld,
-                                                  const PT* __restrict__ prob, size_t prob_ld, QRowMap rm, int n,
+                                                  const float* __restrict__ prob, size_t prob_ld, QRowMap rm, int n,
                                                   const int32_t* __restrict__ d_n, float* __restrict__ policy_out,
                                                   float* __restrict__ value_out, int32_t* __restrict__ act_out,
                                                   uint32_t seed, uint32_t step, int group) {
@@ -108,12 +108,12 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
     const int tiles = (n + kQHeadWaves * 16 - 1) / (kQHeadWaves * 16);
     if ((int)blockIdx.x >= tiles) return;                          // (uniform: a launch sized for the upper bound)
     float* bsm = qsm;
-    const bool he_fold = kImg && p.F < kHeF;                       // (kImg: the folded form; A/B keeps the old one)
-    const float* weS = bsm + (kImg ? 2 * kImgBuf : 2 * kQKC * kQBLd);   // kHeLds: We [kHeF][256] after the staging
+    const bool he_fold = p.F < kHeF;                               // (the bias folded into We: below)
+    const float* weS = bsm + 2 * kImgBuf;                          // kHeLds: We [kHeF][256] after the staging
     if (kHeLds) {
         // We in LDS for the workgroup's life; the bias as one more input row when the features leave one free
         // (k = F: weight be, input 1), so the recomputed tile needs no bias load
-        float* wd = bsm + (kImg ? 2 * kImgBuf : 2 * kQKC * kQBLd);
+        float* wd = bsm + 2 * kImgBuf;
         const int F = p.F;
         for (int i = threadIdx.x; i < kHeF * kAH; i += blockDim.x)
             wd[i] = i < F * kAH ? p.w[2][i] : (he_fold && i < (F + 1) * kAH) ? p.w[3][i - F * kAH] : 0.f;
@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
     const int tid = tid_x(), lane = tid & 63, wid = tid >> 6, h = lane >> 4, c = lane & 15;
     const int base = (tile * kQHeadWaves + wid) * 16;
     const int ia = min(base + c, n - 1);                            // this lane's agent (clamped: junk, never written)
-    const int row = rm.rows ? rm.rows[ia] : ia;
+    const int row = rm.row(ia);
     const int env = rm.rows ? row / rm.rowcap : ia;
     // the weight and image pointers, opaque per tile: else the compiler hoists every chunk's addresses out of the
     // tile loop and spills them
@@ -134,14 +134,9 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
     for (int k = 0; k < kABlocks; ++k) { W[k] = p.w[k]; asm volatile("" : "+s"(W[k])); }
 #pragma unroll
     for (int k = 0; k < kAImg; ++k) { I[k] = p.img[k]; asm volatile("" : "+s"(I[k])); }
-#define MFX_ACNET_GEMM(MT, NCH, ZERO, WB, IB, K, VAT, ACC)                                                              \
-    do {                                                                                                              \
-        if constexpr (kImg) wg_gemm_i<MT, NCH, ZERO>(IB, K, VAT, bsm, ACC);                                          \
-        else wg_gemm_t<MT, NCH, ZERO>(WB, K, VAT, bsm, ACC);                                                         \
-    } while (0)
     // ---- h_view^T [256 x 16]: view floats k = 16 ch + 4 h + s of this lane's agent, two chunks ahead in flight
     f32x4 hv[16];
-    if constexpr (kImg) {
+    {
         // the view rows through LDS: a ring of 3 chunks (64 agents x 16 floats each, after We), filled two chunks
         // ahead by direct-to-LDS loads -- instruction q of wave w: agent 4 (4 w + q) + lane / 16, float lane % 16
         // (columns past V read float V - 1: its weights are zero)
@@ -162,7 +157,7 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int a = min(tile * kQHeadWaves * 16 + 4 * (4 * wid + q) + (lane >> 4), n - 1);
-            vsrc[q] = view + (size_t)(rm.rows ? rm.rows[a] : a) * view_ld;
+            vsrc[q] = view + (size_t)rm.row(a) * view_ld;
         }
         const int V = p.V;
         auto view_issue = [&](int ch) {
@@ -191,33 +186,6 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
         if (!(MFX_ACNET_SKIP & 1))
             wg_gemm_i<16, 0, false, 4>(kPack ? p.vimg : I[0], kPack ? p.vK : p.Vp, vat, bsm, hv,
                                        [&](int ch) { view_issue(ch + 2); });
-    } else {
-        const float* vr = view + (size_t)row * view_ld + 4 * h;
-        const int V = p.V;
-        float b0[4], b1[4], b2[4];
-        auto fetch = [&](int ch, float* b) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const int k = 16 * ch + 4 * h + s;
-                b[s] = k < V ? vr[16 * ch + s] : 0.f;
-            }
-        };
-        fetch(0, b0);
-        fetch(1, b1);
-        int have = -1;
-        auto vat = [&](int ch, int s) {
-            if (s == 0 && have != ch) {                             // rotate: chunk ch in b0, ch + 1 in b1
-                if (have >= 0) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { b0[j] = b1[j]; b1[j] = b2[j]; }
-                }
-                have = ch;
-                fetch(ch + 2, b2);
-            }
-            return b0[s];
-        };
-        bias_init(hv, W[1], h);
-        wg_gemm_t<16, 0, false>(W[0], p.Vp, vat, bsm, hv);
     }
     // the concat's h_view half, activated in place once (relu; the bias was the accumulators' start): read as is by
     // every later layer
@@ -280,37 +248,40 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
         auto dsc = [&](int ch, int s) { return div_tenth(dh[ch][s]); };
         auto dval = [&](int ch, int s) { return dh[ch][s]; };
         bias_init(dh, W[6], h);
-        if (!(MFX_ACNET_SKIP & 2)) MFX_ACNET_GEMM(16, 32, false, W[4], I[1], 2 * kAH, concat_at, dh);
+        if (!(MFX_ACNET_SKIP & 2)) wg_gemm_i<16, 32, false>(I[1], 2 * kAH, concat_at, bsm, dh);
         act_half(0);
-        if (!(MFX_ACNET_SKIP & 4)) MFX_ACNET_GEMM(2, 16, true, W[7], I[3], kAH, dsc, pl);
+        if (!(MFX_ACNET_SKIP & 4)) wg_gemm_i<2, 16, true>(I[3], kAH, dsc, bsm, pl);
         else pl[0] = pl[1] = dh[0];
-        if (!kMF && value_out) MFX_ACNET_GEMM(1, 16, true, W[9], I[5], kAH, dval, vv);
+        if (!kMF && value_out) wg_gemm_i<1, 16, true>(I[5], kAH, dval, bsm, vv);
         bias_init(dh, W[6] + kAH, h);
-        if (!(MFX_ACNET_SKIP & 2)) MFX_ACNET_GEMM(16, 32, false, W[5], I[2], 2 * kAH, concat_at, dh);
+        if (!(MFX_ACNET_SKIP & 2)) wg_gemm_i<16, 32, false>(I[2], 2 * kAH, concat_at, bsm, dh);
         act_half(1);
-        if (!(MFX_ACNET_SKIP & 4)) MFX_ACNET_GEMM(2, 16, false, W[7] + kAH * kAMaxA, I[4], kAH, dsc, pl);
+        if (!(MFX_ACNET_SKIP & 4)) wg_gemm_i<2, 16, false>(I[4], kAH, dsc, bsm, pl);
         else pl[0] += dh[1];
-        if (!kMF && value_out) MFX_ACNET_GEMM(1, 16, false, W[9] + kAH * 16, I[6], kAH, dval, vv);
+        if (!kMF && value_out) wg_gemm_i<1, 16, false>(I[6], kAH, dval, bsm, vv);
     }
     // ---- MF value: emb_prob 64, dense_prob 32, dense 256 over concat(h_view, h_emb, p), value 1
     if (kMF && value_out) {
-        const PT* pr = prob + (size_t)env * prob_ld;
+        const float* pr = prob + (size_t)env * prob_ld;
         const int A = p.A;
         f32x4 e1[4], e2[2];
-        auto pat = [&](int ch, int s) { const int k = 16 * ch + 4 * h + s; return k < A ? (float)pr[k] : 0.f; };
-        MFX_ACNET_GEMM(4, 0, true, W[11], I[7], p.Ap, pat, e1);
+        auto pat = [&](int ch, int s) { const int k = 16 * ch + 4 * h + s; return k < A ? pr[k] : 0.f; };
+        wg_gemm_i<4, 0, true>(I[7], p.Ap, pat, bsm, e1);
         auto e1at = [&](int ch, int s) { return relu_unit(e1, W[12], ch, s); };
-        MFX_ACNET_GEMM(2, 4, true, W[13], I[8], 64, e1at, e2);
+        wg_gemm_i<2, 4, true>(I[8], 64, e1at, bsm, e2);
         f32x4 vd[16];
         auto vdat = [&](int ch, int s) { return ch < 32 ? concat_at(ch, s) : relu_unit(e2, W[14], ch - 32, s); };
-        MFX_ACNET_GEMM(16, 34, true, W[15], I[9], 2 * kAH + 32, vdat, vd);
+        wg_gemm_i<16, 34, true>(I[9], 2 * kAH + 32, vdat, bsm, vd);
         auto voat = [&](int ch, int s) { return relu_unit(vd, W[16], ch, s); };
-        MFX_ACNET_GEMM(1, 16, true, W[17], I[10], kAH, voat, vv);
+        wg_gemm_i<1, 16, true>(I[10], kAH, voat, bsm, vv);
     }
     const int i = base + c;
     if (value_out && h == 0 && i < n) value_out[i] = vv[0][0] + W[kMF ? 18 : 10][0];   // unit 0: lanes h == 0, r 0
     // ---- policy: logits of agent c, actions 16 t + 4 h + r, through LDS to lane c of the wave (h == 0): softmax,
-    // clip, the draw
+    // clip, the draw.  Written out, not a call of policy_act.h's ac_epilogue / draw_running_sum / QRowMap::slot (the
+    // same rule; tests/test_acnet_bf16_gpu.py and tests/acnet_ref.py hold both to one restatement): this kernel sits at
+    // 256 VGPRs with SGPRs parked in VGPR lanes, and any of those calls here reorders its scalar preamble, which cost
+    // 8 B/lane of scratch in the value forms and 0.5-0.9 % of its time (profiles/policy_act_resources.txt).
     float* lg = bsm + wid * 16 * kAMaxA;                             // (the staging buffer is free: wg_gemm_t ended
 #pragma unroll                                                       //  with a barrier)
     for (int t = 0; t < 2; ++t)
@@ -356,7 +327,6 @@ __global__ void __launch_bounds__(256, kHeLds ? 2 : 1) k_acnet(ACNetDev p, const
     }
     __syncthreads();                                                 // (lg and the staging buffers: the next tile's)
     }
-#undef MFX_ACNET_GEMM
 }
 
 }  // namespace mfx
@@ -599,12 +569,21 @@ MFX_API int mfx_acnet_input_support_size(void* handle, int* k) {
     return 0;
 }
 
+// A forward needs weights (include/magent_amd.h): before the first mfx_acnet_set_weights the blob and its images are
+// bare allocations.
+static int acnet_weights(const ACNetHandle* q) {
+    const bool b16 = q->precision == 1;
+    if (q->imaged && (!b16 || q->b16_imaged)) return 0;
+    return fail("acnet: the %s forward needs weights (mfx_acnet_set_weights)", b16 ? "bf16" : "f32");
+}
+
 static int acnet_run(ACNetHandle* q, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
                      const float* prob, size_t prob_ld, QRowMap rm, int n, const int32_t* d_n,
                      float* policy, float* value, int32_t* act, uint32_t seed, uint32_t step, int group, hipStream_t st) {
+    if (q->precision == 1 && value)
+        return fail("acnet: bf16 is acting only (no value head; mfx_acnet_set_precision(0) for the value)");
+    MFX_CHECK(acnet_weights(q));
     if (q->precision == 1) {                                        // the policy path only; the support is not used
-        if (value) return fail("acnet: bf16 is acting only (no value head; mfx_acnet_set_precision(0) for the value)");
-        if (!q->b16_imaged) return fail("acnet: the bf16 forward needs weights (mfx_acnet_set_weights)");
         MFX_HIP(acb16_forward(q->b16, view, view_ld, feat, feat_ld, rm, n, d_n, policy, act, seed, step, group, st));
         return 0;
     }
@@ -613,27 +592,22 @@ static int acnet_run(ACNetHandle* q, const float* view, size_t view_ld, const fl
     // persistent workgroups: as many as the CUs hold at once (two per CU with h_emb in LDS), at most one per tile
     int grid = (n + 16 * kQHeadWaves - 1) / (16 * kQHeadWaves);
     const bool lds = q->dev.Fp <= kHeF;                             // (wider features: h_emb held in registers)
-    const bool img = q->imaged;
     grid = std::min(grid, (lds ? 2 : 1) * device_cus());
-#define MFX_ACNET_LAUNCH1(MF, LDS, IMG, PK)                                                                            \
-    k_acnet<float, MF, LDS, IMG, PK><<<grid, 256, acnet_smem(LDS, IMG), st>>>(                                         \
+    // (the packed view order: h_emb in LDS and a support set)
+#define MFX_ACNET_LAUNCH(MF, LDS, PK)                                                                                  \
+    k_acnet<MF, LDS, PK><<<grid, 256, kAcnetSmem, st>>>(                                                               \
         q->dev, view, view_ld, feat, feat_ld, prob, prob_ld, rm, n, d_n, policy, value, act, seed, step, group)
-    // (the packed view order: the image path with h_emb in LDS -- the view-ring form -- and a support set)
-#define MFX_ACNET_LAUNCH(MF, LDS)                                                                                      \
+#define MFX_ACNET_FORM(MF)                                                                                             \
     do {                                                                                                              \
-        if (img && LDS && q->dev.vdesc) MFX_ACNET_LAUNCH1(MF, LDS, true, LDS);                                       \
-        else if (img) MFX_ACNET_LAUNCH1(MF, LDS, true, false);                                                        \
-        else MFX_ACNET_LAUNCH1(MF, LDS, false, false);                                                                \
+        if (lds && q->dev.vdesc) MFX_ACNET_LAUNCH(MF, true, true);                                                    \
+        else if (lds) MFX_ACNET_LAUNCH(MF, true, false);                                                              \
+        else MFX_ACNET_LAUNCH(MF, false, false);                                                                      \
     } while (0)
     // (kMF selects only the value head: without value_out both forms compute the same policy, and the plain one
     // holds fewer registers)
-    if (value && q->dev.use_mf) {
-        if (lds) MFX_ACNET_LAUNCH(true, true); else MFX_ACNET_LAUNCH(true, false);
-    } else {
-        if (lds) MFX_ACNET_LAUNCH(false, true); else MFX_ACNET_LAUNCH(false, false);
-    }
+    if (value && q->dev.use_mf) MFX_ACNET_FORM(true); else MFX_ACNET_FORM(false);
+#undef MFX_ACNET_FORM
 #undef MFX_ACNET_LAUNCH
-#undef MFX_ACNET_LAUNCH1
     MFX_HIP(hipGetLastError());
     return 0;
 }
@@ -656,6 +630,7 @@ MFX_API int mfx_acnet_act_rollout(void* handle, const float* d_view, const float
                                   uint32_t seed, uint32_t step, void* stream) {
     auto* q = static_cast<ACNetHandle*>(handle);
     hipStream_t st = (hipStream_t)stream;
+    MFX_CHECK(acnet_weights(q));                                    // (before the row list is launched)
     MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
     QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap};
     return acnet_run(q, d_view, q->dev.V, d_feat, q->dev.F, nullptr, 0, rm, E * rowcap, d_total, nullptr, nullptr,

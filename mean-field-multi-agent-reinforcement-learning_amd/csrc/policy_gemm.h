@@ -36,7 +36,7 @@ constexpr int kQHeadWaves = 4, kQKC = 16;                // agents per wave = 16
 __host__ __device__ constexpr int qhead_p(int mt) { return ((mt + 3) & ~3) + (mt >= 8 ? 4 : 0); }
 constexpr int kQMaxMT = 16;                              // the widest layer: 256 output units
 constexpr int kQBLd = 16 * qhead_p(kQMaxMT);             // the widest staged row (256 units: 320 floats)
-constexpr size_t kQHeadSmem = (size_t)2 * kQKC * kQBLd * 4;
+constexpr size_t kQStageSmem = (size_t)2 * kQKC * kQBLd * 4;   // wg_gemm_t's two staged chunks (from offset 0)
 
 // threadIdx.x, opaque to loop-invariant code motion: in a persistent kernel's tile loop the compiler would otherwise
 // hoist every chunk's lane-derived addresses out of the loop and spill them (k_acnet: 3.8 KB of scratch).
@@ -251,15 +251,6 @@ __device__ __forceinline__ float relu_unit(const f32x4* acc, const float* __rest
     const int h = (tid_x() & 63) >> 4;
     return fmaxf(acc[t][s] + bias[16 * t + 4 * h + s], 0.f);
 }
-
-// Compact agent i -> (view row, action slot, prob row): rows == null: (i, i, i); else row = rows[i]
-// = e * rowcap + j of a rollout buffer, action slot e * act_env + act_off + j, prob row e -- or, with prob_by_row
-// (a mean action per agent: the neighbourhood mean, neighbor_kernels.hip), the rollout row e * rowcap + j itself.
-struct QRowMap {
-    const int32_t* rows;
-    int rowcap, act_env, act_off;
-    int prob_by_row;
-};
 
 // The compact row list of one group of a rollout batch (policy_kernels.hip k_qnet_rows): rows e * rowcap + j for
 // j < min(n_e, rowcap) in env order, and their count in total[0] -- on the device, nothing read back.  total: 1 +

@@ -20,7 +20,8 @@
 //                (ky, kx) block) and its 81st position on the VALU; the 2,592 activations to HBM (10 KB/agent)
 //   k_qnet_head  four waves x 16 agents per workgroup: every layer transposed (weights as the A operand),
 //                so each layer's accumulators are the next layer's B operand in registers; the weight
-//                chunks staged in LDS and shared by the four waves; the Q values and the argmax
+//                chunks staged in LDS and shared by the four waves; the Q values and the argmax (or the draw):
+//                qsample.h q_epilogue, shared with the bf16 head
 // A and B operands of v_mfma_f32_16x16x4_f32: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15];
 // D: lane l holds D[(l >> 4) * 4 + r][l & 15], r = 0..3 (cdna_hip_programming.md, fragment layout).
 #include <hip/hip_runtime.h>
@@ -29,8 +30,10 @@
 
 #include <algorithm>
 #include <cmath>
+#include <map>
 
 #include "mfx_common.h"
+#include "policy_act.h"
 #include "policy_gemm.h"
 #include "qnet_bf16.h"
 #include "qsample.h"
@@ -265,13 +268,13 @@ __global__ void __launch_bounds__(512, 1) k_qnet_conv2(QNetDev p, const float* _
 
 // ------------------------------------------------------------------------------------------ head
 
-// kImg (the default): Dense-Obs over its weight image (wg_gemm_i, direct-to-LDS chunks) with the conv activations
-// through an LDS ring filled two chunks ahead, its accumulators starting at the bias; else (no weights set yet) the
-// register-staged wg_gemm_t.  LDS: the image path's 32 KB of chunks + the 12 KB ring, then the small layers'
-// wg_gemm_t staging from offset 0.
-constexpr size_t kQHeadImgSmem = kImgSmem + 3 * 1024 * 4 > kQHeadSmem ? kImgSmem + 3 * 1024 * 4 : kQHeadSmem;
+// Dense-Obs over its weight image (wg_gemm_i, direct-to-LDS chunks; made by set_weights, without which qnet_run
+// refuses the call) with the conv activations through an LDS ring filled two chunks ahead, its accumulators starting at
+// the bias.  LDS: the 32 KB of chunks + the 12 KB ring, then the small layers' wg_gemm_t staging from offset 0.
+constexpr size_t kQHeadSmem = kImgSmem + 3 * 1024 * 4;
+static_assert(kQHeadSmem >= kQStageSmem, "the small layers stage through wg_gemm_t");
 // kSample: the Boltzmann draw of qsample.h in place of the argmax (qs; the greedy instantiations never read it).
-template <typename PT, bool kImg, bool kSample>
+template <typename PT, bool kSample>
 __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __restrict__ conv, int n,
                                                       const float* __restrict__ feat, size_t feat_ld,
                                                       const PT* __restrict__ prob, size_t prob_ld, QRowMap rm,
@@ -284,11 +287,10 @@ __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, h = lane >> 4, c = lane & 15;
     const int base = (blockIdx.x * kQHeadWaves + wid) * 16;
     const int ia = min(base + c, n - 1);                 // this lane's agent (clamped: junk rows, never written)
-    const int row = rm.rows ? rm.rows[ia] : ia;
-    const int env = rm.rows ? (rm.prob_by_row ? row : row / rm.rowcap) : ia;     // the prob row
+    const int row = rm.row(ia), env = rm.prob_row(row);
     // ---- Dense-Obs^T [256 x 16]: the conv activations of this lane's agent, 4 consecutive per chunk step
     f32x4 hobs[16];
-    if constexpr (kImg) {
+    {
         // the activation rows through LDS: a ring of 3 chunks (64 agents x 16 floats each), filled two chunks ahead
         // by direct-to-LDS loads -- instruction q of wave w: agent 4 (4 w + q) + lane / 16, float lane % 16
         float* ring = bsm + 2 * kImgBuf;
@@ -317,18 +319,6 @@ __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __
         for (int t = 0; t < 16; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) hobs[t][r] = fmaxf(hobs[t][r], 0.f);
-    } else {
-        const float4* ar = reinterpret_cast<const float4*>(conv + (size_t)ia * kQFlat) + h;   // k = 16 ch + 4 h + s
-        float4 cur4 = ar[0], nxt4 = cur4;
-        int have = 0;
-        wg_gemm_t<16>(p.wd, kQFlat, [&](int ch, int s) {
-            if (s == 0) {                                // chunk ch's four values; chunk ch + 1's in flight
-                if (have != ch) cur4 = nxt4;
-                have = ch;
-                if ((ch + 1) * kQKC < kQFlat) nxt4 = ar[(ch + 1) * 4];
-            }
-            return s == 0 ? cur4.x : s == 1 ? cur4.y : s == 2 ? cur4.z : cur4.w;
-        }, bsm, hobs);
     }
     // ---- Dense-Emb^T [32 x 16]
     f32x4 hemb[2];
@@ -352,7 +342,7 @@ __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __
     // 16-17 h_emb, 18-19 h_prob
     f32x4 d2[8];
     wg_gemm_t<8, (kQHObs + kQHEmb + kQHP2) / 16>(p.w2d, p.Kc, [&](int ch, int s) {
-        if (ch < 16) return kImg ? hobs[ch][s] : relu_unit(hobs, p.bd, ch, s);   // (kImg: activated in place)
+        if (ch < 16) return hobs[ch][s];                 // (activated in place)
         if (ch < 18) return relu_unit(hemb, p.be, ch - 16, s);
         return relu_unit(hp, p.bp2, ch - 18, s);
     }, bsm, d2);
@@ -360,53 +350,16 @@ __global__ void __launch_bounds__(256, 2) k_qnet_head(QNetDev p, const float* __
     wg_gemm_t<4, kQH2 / 16>(p.wo, kQH2, [&](int ch, int s) { return relu_unit(d2, p.b2d, ch, s); }, bsm, d3);
     f32x4 qv[2];
     wg_gemm_t<2, kQHOut / 16>(p.wq, kQHOut, [&](int ch, int s) { return relu_unit(d3, p.bo, ch, s); }, bsm, qv);
-    // ---- Q values: lane (h, c) holds actions 16 t + 4 h + r of agent c; argmax (first maximum) over the
-    // four lanes of the agent
+    // ---- Q values: lane (h, c) holds actions 16 t + 4 h + r of agent c; the bias, then q_epilogue
     const int A = p.A;
-    float best = -__builtin_huge_valf();
-    int bi = 1 << 30;
-    const int i = base + c;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int a = 16 * t + 4 * h + r;
-            if (a < A) {
-                const float x = qv[t][r] + p.bq[a];
-                if (q_out && i < n) q_out[(size_t)i * A + a] = x;
-                if constexpr (kSample) qv[t][r] = x;
-                else if (x > best || (x == best && a < bi)) { best = x; bi = a; }
-            }
+            if (a < A) qv[t][r] += p.bq[a];
         }
-    if constexpr (kSample) {
-        // the agent's row gathered from its four lanes (every lane of the agent gets it; lane h == 0 uses it): the
-        // draw sums the weights in ascending action order
-        float x[kQSMaxA];
-#pragma unroll
-        for (int a = 0; a < kQSMaxA; ++a) x[a] = __shfl(qv[a >> 4][a & 3], 16 * ((a >> 2) & 3) + c);
-        if (h == 0 && i < n) {
-            // the uniform's row: the rollout row e * rowcap + j, or the row of the whole dense batch
-            bi = q_sample_row(x, A, qs.T, ac_uniform(qs.seed, qs.step, qs.group, rm.rows ? row : n_off + i));
-            if (qs.w) {
-                float* wr = qs.w + (size_t)i * A;
-#pragma unroll
-                for (int a = 0; a < kQSMaxA; ++a)
-                    if (a < A) wr[a] = x[a];
-            }
-        }
-    } else {
-#pragma unroll
-        for (int o = 16; o < 64; o <<= 1) {              // lanes c, c + 16, c + 32, c + 48
-            const float ob = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bi, o);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
-    }
-    if (h == 0 && i < n && act_out) {
-        const int r = rm.rows ? rm.rows[i] : i;
-        const size_t slot = rm.rows ? (size_t)(r / rm.rowcap) * rm.act_env + rm.act_off + r % rm.rowcap : (size_t)i;
-        act_out[slot] = bi;
-    }
+    q_epilogue<kSample>(qv, A, base + c, n, row, n_off, h, c, rm, q_out, act_out, qs);
 }
 
 // ------------------------------------------------------------------------------------------ rollout rows
@@ -475,7 +428,9 @@ struct QNetHandle {
     QNetDev dev{};
     float* blob = nullptr;
     size_t blob_n = 0;
-    DevBuf<float> conv;           // [n][2592] activations between the kernels
+    // [n][2592] activations between the kernels, one buffer per stream: callers on different streams (two engines
+    // that share this network) do not overwrite each other's pass
+    std::map<hipStream_t, DevBuf<float>> conv;
     float* img = nullptr;         // Dense-Obs's weight image (made by set_weights)
     bool imaged = false;
     int precision = 0;            // 0: f32 (the kernels above), 1: bf16 operands (qnet_bf16_kernels.hip)
@@ -590,16 +545,25 @@ MFX_API int mfx_qnet_precision(void* handle, int* precision) {
 // (10 KB per agent: 2.7 GB at this size).
 constexpr int kQPass = 1 << 18;
 
+// A forward needs weights (include/magent_amd.h): before the first mfx_qnet_set_weights the blob and its images are
+// bare allocations.
+static int qnet_weights(const QNetHandle* q) {
+    const bool b16 = q->precision == 1;
+    if (q->imaged && (!b16 || q->b16_imaged)) return 0;
+    return fail("qnet: the %s forward needs weights (mfx_qnet_set_weights)", b16 ? "bf16" : "f32");
+}
+
 // n rows (d_n: the count on the device, n its upper bound -- nothing is read back; launches sized for n).
 static int qnet_run(QNetHandle* q, const float* view, size_t view_ld, const float* feat, size_t feat_ld,
                     const void* prob, int prob_f64, size_t prob_ld, QRowMap rm, int n, float* q_out, int32_t* act,
                     hipStream_t st, const int32_t* d_n = nullptr, const QSample* qs = nullptr) {
     if (n <= 0) return 0;
     if (q->dev.use_mf && !prob) return fail("qnet: the mean-field net needs prob");
+    MFX_CHECK(qnet_weights(q));
     const bool b16 = q->precision == 1;
-    if (b16 && !q->b16_imaged) return fail("qnet: the bf16 forward needs weights (mfx_qnet_set_weights)");
     // (bf16: the pass buffer holds 2-byte activations, half the floats)
-    try { q->conv.ensure((size_t)std::min(n, kQPass) * (b16 ? kQFlat / 2 : kQFlat)); } catch (const HipFailure& f) { return fail("%s", f.what()); }
+    DevBuf<float>& conv = q->conv[st];
+    try { conv.ensure((size_t)std::min(n, kQPass) * (b16 ? kQFlat / 2 : kQFlat)); } catch (const HipFailure& f) { return fail("%s", f.what()); }
     int dev = 0, cus = 0;
     MFX_HIP(hipGetDevice(&dev));
     MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -622,25 +586,52 @@ static int qnet_run(QNetHandle* q, const float* view, size_t view_ld, const floa
         }
         if (b16) {
             MFX_HIP(qb16_forward(q->b16, v, view_ld, f, feat_ld, pb, prob_f64, prob_ld, r, m,
-                                 reinterpret_cast<uint16_t*>(q->conv.p), qo, ao, d_n, off, st, qs ? &s : nullptr));
+                                 reinterpret_cast<uint16_t*>(conv.p), qo, ao, d_n, off, st, qs ? &s : nullptr));
             continue;
         }
         const int cgrid = std::min((m + kQConv2Agents - 1) / kQConv2Agents, cus);
-        k_qnet_conv2<<<cgrid, 512, kQConvSmem, st>>>(q->dev, v, view_ld, r.rows, m, q->conv.p, d_n, off);
+        k_qnet_conv2<<<cgrid, 512, kQConvSmem, st>>>(q->dev, v, view_ld, r.rows, m, conv.p, d_n, off);
         MFX_HIP(hipGetLastError());
         const int hgrid = (m + 16 * kQHeadWaves - 1) / (16 * kQHeadWaves);
-        const bool img = q->imaged;
-#define MFX_QHEAD(PT, IMG, SMP)                                                                                    \
-        k_qnet_head<PT, IMG, SMP><<<hgrid, 256, IMG ? kQHeadImgSmem : kQHeadSmem, st>>>(                             \
-            q->dev, q->conv.p, m, f, feat_ld, static_cast<const PT*>(pb), prob_ld, r, qo, ao, d_n, off, s)
-#define MFX_QHEAD_I(PT, SMP) do { if (img) MFX_QHEAD(PT, true, SMP); else MFX_QHEAD(PT, false, SMP); } while (0)
-        if (qs) { if (prob_f64) MFX_QHEAD_I(double, true); else MFX_QHEAD_I(float, true); }
-        else { if (prob_f64) MFX_QHEAD_I(double, false); else MFX_QHEAD_I(float, false); }
-#undef MFX_QHEAD_I
+#define MFX_QHEAD(PT, SMP)                                                                                         \
+        k_qnet_head<PT, SMP><<<hgrid, 256, kQHeadSmem, st>>>(                                                        \
+            q->dev, conv.p, m, f, feat_ld, static_cast<const PT*>(pb), prob_ld, r, qo, ao, d_n, off, s)
+        if (qs) { if (prob_f64) MFX_QHEAD(double, true); else MFX_QHEAD(float, true); }
+        else { if (prob_f64) MFX_QHEAD(double, false); else MFX_QHEAD(float, false); }
 #undef MFX_QHEAD
         MFX_HIP(hipGetLastError());
     }
     return 0;
+}
+
+// Group g of a rollout batch: the compact row list (d_rows, its count d_total: on the device, nothing read back), the
+// row map, then the forward launched for the upper bound E * rowcap.  qs: the Boltzmann draw (its group is g); null:
+// greedy.
+struct QProbSrc {                   // the mean action a rollout row reads
+    const void* p;
+    int f64;                        // float64 (the rollout's mean actions), else float32
+    size_t ld;
+    int by_row;                     // QRowMap::prob_by_row
+};
+// the env's row of group g of d_mean [E][G][mean_stride] float64
+static QProbSrc qprob_env(const double* d_mean, int mean_stride, int G, int g) {
+    return {d_mean + (size_t)g * mean_stride, 1, (size_t)G * mean_stride, 0};
+}
+// the agent's own row of d_prob_rows [E][rowcap][A] float32
+static QProbSrc qprob_rows(void* handle, const float* d_prob_rows) {
+    return {d_prob_rows, 0, (size_t)static_cast<QNetHandle*>(handle)->dev.A, 1};
+}
+
+static int qnet_act_rollout(void* handle, const float* d_view, const float* d_feat, const int32_t* d_counts,
+                            QProbSrc prob, int E, int G, int g, int rowcap, int32_t* d_rows, int32_t* d_total,
+                            int32_t* d_act, void* stream, const QSample* qs) {
+    auto* q = static_cast<QNetHandle*>(handle);
+    hipStream_t st = (hipStream_t)stream;
+    MFX_CHECK(qnet_weights(q));                          // (before the row list is launched)
+    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
+    const QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap, prob.by_row};
+    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, prob.p, prob.f64, prob.ld, rm, E * rowcap, nullptr, d_act, st,
+                    d_total, qs);
 }
 
 // The compact row list act_rollout builds (k_rows_chunk + k_qnet_rows), on its own: rows of group g of [E][G] counts.
@@ -668,12 +659,8 @@ MFX_API int mfx_qnet_forward(void* handle, const float* d_view, const float* d_f
 MFX_API int mfx_qnet_act_rollout(void* handle, const float* d_view, const float* d_feat, const int32_t* d_counts,
                                  const double* d_mean, int mean_stride, int E, int G, int g, int rowcap,
                                  int32_t* d_rows, int32_t* d_total, int32_t* d_act, void* stream) {
-    auto* q = static_cast<QNetHandle*>(handle);
-    hipStream_t st = (hipStream_t)stream;
-    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
-    QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap};
-    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_mean + (size_t)g * mean_stride, 1, (size_t)G * mean_stride,
-                    rm, E * rowcap, nullptr, d_act, st, d_total);
+    return qnet_act_rollout(handle, d_view, d_feat, d_counts, qprob_env(d_mean, mean_stride, G, g), E, G, g, rowcap,
+                            d_rows, d_total, d_act, stream, nullptr);
 }
 
 // mfx_qnet_act_rollout with a mean action per agent (the neighbourhood mean): row e * rowcap + j reads
@@ -681,12 +668,8 @@ MFX_API int mfx_qnet_act_rollout(void* handle, const float* d_view, const float*
 MFX_API int mfx_qnet_act_rollout_rows(void* handle, const float* d_view, const float* d_feat, const int32_t* d_counts,
                                       const float* d_prob_rows, int E, int G, int g, int rowcap, int32_t* d_rows,
                                       int32_t* d_total, int32_t* d_act, void* stream) {
-    auto* q = static_cast<QNetHandle*>(handle);
-    hipStream_t st = (hipStream_t)stream;
-    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
-    QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap, 1};
-    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_prob_rows, 0, q->dev.A, rm, E * rowcap, nullptr, d_act, st,
-                    d_total);
+    return qnet_act_rollout(handle, d_view, d_feat, d_counts, qprob_rows(handle, d_prob_rows), E, G, g, rowcap, d_rows,
+                            d_total, d_act, stream, nullptr);
 }
 
 // The Boltzmann acting mode (qsample.h): refused before anything is launched unless T is finite and > 0.
@@ -714,14 +697,10 @@ MFX_API int mfx_qnet_act_rollout_sample(void* handle, const float* d_view, const
                                         const double* d_mean, int mean_stride, int E, int G, int g, int rowcap,
                                         int32_t* d_rows, int32_t* d_total, int32_t* d_act, float temperature,
                                         uint32_t seed, uint32_t step, void* stream) {
-    auto* q = static_cast<QNetHandle*>(handle);
     MFX_CHECK(qsample_temperature("qnet_act_rollout_sample", temperature));
-    hipStream_t st = (hipStream_t)stream;
-    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
-    QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap};
     const QSample qs{temperature, seed, step, g, nullptr};
-    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_mean + (size_t)g * mean_stride, 1, (size_t)G * mean_stride,
-                    rm, E * rowcap, nullptr, d_act, st, d_total, &qs);
+    return qnet_act_rollout(handle, d_view, d_feat, d_counts, qprob_env(d_mean, mean_stride, G, g), E, G, g, rowcap,
+                            d_rows, d_total, d_act, stream, &qs);
 }
 
 // mfx_qnet_act_rollout_sample with a mean action per agent (mfx_qnet_act_rollout_rows' d_prob_rows).
@@ -729,14 +708,10 @@ MFX_API int mfx_qnet_act_rollout_rows_sample(void* handle, const float* d_view, 
                                              const int32_t* d_counts, const float* d_prob_rows, int E, int G, int g,
                                              int rowcap, int32_t* d_rows, int32_t* d_total, int32_t* d_act,
                                              float temperature, uint32_t seed, uint32_t step, void* stream) {
-    auto* q = static_cast<QNetHandle*>(handle);
     MFX_CHECK(qsample_temperature("qnet_act_rollout_rows_sample", temperature));
-    hipStream_t st = (hipStream_t)stream;
-    MFX_HIP(launch_rollout_rows(d_counts, E, G, g, rowcap, d_rows, d_total, st));
-    QRowMap rm{d_rows, rowcap, G * rowcap, g * rowcap, 1};
     const QSample qs{temperature, seed, step, g, nullptr};
-    return qnet_run(q, d_view, kQViewF, d_feat, q->dev.F, d_prob_rows, 0, q->dev.A, rm, E * rowcap, nullptr, d_act, st,
-                    d_total, &qs);
+    return qnet_act_rollout(handle, d_view, d_feat, d_counts, qprob_rows(handle, d_prob_rows), E, G, g, rowcap, d_rows,
+                            d_total, d_act, stream, &qs);
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@
 //         Dense2 out, Dense-Out out.
 //   * Products are accumulated in f32 (the MFMA accumulator, which starts at the f32 bias); ReLU is applied in f32.
 //   * The Q values are written in f32, unrounded.  Argmax takes the first maximum; the opt-in Boltzmann draw
-//     (k_qb16_head<.., true>) is qsample.h's, in f32 on those Q values.
+//     (k_qb16_head<.., true>) is qsample.h's, in f32 on those Q values (q_epilogue: k_qnet_head's).
 //   * An agent's result does not depend on its position in the batch or on the batch size: every agent is one
 //     column of its MFMAs, accumulated in one fixed order.
 //
@@ -29,7 +29,8 @@
 //                (double buffered through registers) and shared by the four waves, each fragment read feeding two
 //                MFMAs (the wave's two agent tiles); the activations straight from HBM, 16 B per lane and step, a
 //                step ahead.  The small layers chain in registers (pack_relu: two accumulator tiles -> one B
-//                fragment), their weight fragments read from the images in L2.  Epilogue and row map: k_qnet_head's.
+//                fragment), their weight fragments read from the images in L2.  Epilogue and row map:
+//                k_qnet_head's, the same functions (qsample.h q_epilogue, policy_act.h QRowMap).
 // No scratch, no spills (tests/test_policy_bf16_cpu.py); LDS 40 KB (conv) and 32 KB (head) per workgroup, two
 // workgroups per CU.
 #include <hip/hip_runtime.h>
@@ -242,8 +243,8 @@ k_qb16_head(QB16Net p, const uint16_t* __restrict__ act, int n, const float* __r
     for (int a = 0; a < 2; ++a) {
         base[a] = ((blockIdx.x * kB16HeadWaves + wid) * kB16HeadTiles + a) * 16;
         ia[a] = min(base[a] + c, n - 1);                 // this lane's agents (clamped: junk columns, never written)
-        row[a] = rm.rows ? rm.rows[ia[a]] : ia[a];
-        env[a] = rm.rows ? (rm.prob_by_row ? row[a] : row[a] / rm.rowcap) : ia[a];     // the prob row
+        row[a] = rm.row(ia[a]);
+        env[a] = rm.prob_row(row[a]);
     }
     // ---- Dense-Obs^T [256 x 32 agents]: k-step s = conv position s; this lane's 8 activations of it: 16 B at 8 h
     f32x4 hobs[2][16];
@@ -358,53 +359,10 @@ k_qb16_head(QB16Net p, const uint16_t* __restrict__ act, int n, const float* __r
 #pragma unroll
     for (int s = 0; s < 2; ++s)
         layer_step<2>(qv, p.wq, s, lane, pack_relu(d3[0][2 * s], d3[0][2 * s + 1]), pack_relu(d3[1][2 * s], d3[1][2 * s + 1]));
-    // ---- Q values: lane (h, c) holds actions 16 t + 4 h + r of agent c; argmax (first maximum) over the agent's
-    // four lanes
-    const int A = p.A;
+    // ---- Q values (the accumulators started at the bias): q_epilogue per agent tile
 #pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        float best = -__builtin_huge_valf();
-        int bi = 1 << 30;
-        const int i = base[a] + c;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int u = 16 * t + 4 * h + r;
-                if (u < A) {
-                    const float x = qv[a][t][r];
-                    if (q_out && i < n) q_out[(size_t)i * A + u] = x;
-                    if (x > best || (x == best && u < bi)) { best = x; bi = u; }
-                }
-            }
-        if constexpr (kSample) {
-            // the agent's row gathered from its four lanes (lane h == 0 uses it), as k_qnet_head does
-            float x[kQSMaxA];
-#pragma unroll
-            for (int u = 0; u < kQSMaxA; ++u) x[u] = __shfl(qv[a][u >> 4][u & 3], 16 * ((u >> 2) & 3) + c);
-            if (h == 0 && i < n) {
-                bi = q_sample_row(x, A, qs.T, ac_uniform(qs.seed, qs.step, qs.group, rm.rows ? row[a] : n_off + i));
-                if (qs.w) {
-                    float* wr = qs.w + (size_t)i * A;
-#pragma unroll
-                    for (int u = 0; u < kQSMaxA; ++u)
-                        if (u < A) wr[u] = x[u];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int o = 16; o < 64; o <<= 1) {          // lanes c, c + 16, c + 32, c + 48
-                const float ob = __shfl_xor(best, o);
-                const int oi = __shfl_xor(bi, o);
-                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-            }
-        }
-        if (h == 0 && i < n && act_out) {
-            const int r = rm.rows ? rm.rows[i] : i;
-            const size_t slot = rm.rows ? (size_t)(r / rm.rowcap) * rm.act_env + rm.act_off + r % rm.rowcap : (size_t)i;
-            act_out[slot] = bi;
-        }
-    }
+    for (int a = 0; a < 2; ++a)
+        q_epilogue<kSample>(qv[a], p.A, base[a] + c, n, row[a], n_off, h, c, rm, q_out, act_out, qs);
 }
 
 // K (rows read; the blob pads them with zero rows to a multiple of 4) and unit tiles of the nine matrices

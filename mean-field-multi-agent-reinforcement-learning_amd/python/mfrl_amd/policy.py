@@ -61,6 +61,28 @@ def _stream():
     return _P(torch.cuda.current_stream().cuda_stream)
 
 
+def _u32(x):
+    return ctypes.c_uint32(x & 0xFFFFFFFF)
+
+
+def _rollout_args(scratch, eng, group, names):
+    """What an act_rollout call reads of engine `eng`: the pointers of its rollout buffers `names` (the group's view
+    and feature, the batch's counts, mean actions and actions) and the row-list scratch (rows pointer, total pointer).
+    The scratch, rows_scratch(E, rowcap) ints, is kept in the dict `scratch` per engine, so engines on different
+    streams may share one network."""
+    E, rc = eng.n_envs, eng.rowcap
+    rows = scratch.get(id(eng))
+    if rows is None or rows.numel() < rows_scratch(E, rc):
+        rows = scratch[id(eng)] = torch.empty(rows_scratch(E, rc), dtype=torch.int32, device="cuda")
+    ptr = {}
+    for name in names:
+        p, nb = _P(), ctypes.c_size_t()
+        eng._check(eng._dll.mfx_battle_rollout_buffer(eng.game, name.encode(), group if name in ("view", "feature")
+                                                      else 0, ctypes.byref(p), ctypes.byref(nb)), "rollout_buffer")
+        ptr[name] = p
+    return ptr, _P(rows.data_ptr()), _P(rows.data_ptr() + 4 * E * rc)
+
+
 PRECISIONS = {"f32": 0, "bf16": 1}      # mfx_qnet_set_precision / mfx_acnet_set_precision
 
 N_BLOCKS = 18      # w1 b1 w2 b2 wd bd we be wp1 bp1 wp2 bp2 w2d b2d wo bo wq bq (policy_kernels.hip)
@@ -176,7 +198,7 @@ class QNetHIP:
         check(L.mfx_qnet_create(int(h), int(w), int(c), self.F, self.A, int(self.use_mf), ctypes.byref(hdl)),
               "mfx_qnet_create")
         self.handle = hdl
-        self._rows = None
+        self._rows = {}
         if precision != "f32":
             check(L.mfx_qnet_set_precision(hdl, PRECISIONS[precision], _P()), "mfx_qnet_set_precision")
 
@@ -218,8 +240,8 @@ class QNetHIP:
             w = torch.empty((n, self.A), dtype=torch.float32, device=view.device) if want_w else None
             check(self._L.mfx_qnet_forward_sample(self.handle, _ptr(view), _ptr(feature),
                                                   _ptr(prob if self.use_mf else None), int(n), _ptr(q), _ptr(w), _ptr(act),
-                                                  ctypes.c_float(temperature), ctypes.c_uint32(seed & 0xFFFFFFFF),
-                                                  ctypes.c_uint32(step & 0xFFFFFFFF), _stream()),
+                                                  ctypes.c_float(temperature), _u32(seed),
+                                                  _u32(step), _stream()),
                   "mfx_qnet_forward_sample")
             return (q, act, w) if want_w else (q, act)
         check(self._L.mfx_qnet_forward(self.handle, _ptr(view), _ptr(feature), _ptr(prob if self.use_mf else None),
@@ -240,43 +262,28 @@ class QNetHIP:
 
         Works on every plan that takes a learned policy (BattleBatch.rollout_policy_path: all but
         MFX_ROLLOUT_PIPE=1 -- large batches, large envs and few-env batches alike; E, rowcap and the buffers come
-        from the engine).  The observation must be current: call eng.rollout_policy_observe() after rollout_init,
+        from the engine; the row-list scratch is per engine, so engines on different streams may share this network).
+        The observation must be current: call eng.rollout_policy_observe() after rollout_init,
         rollout_step or any per-call API use, before the first act_rollout / rollout_policy_step pair."""
         E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
-        if self._rows is None or self._rows.numel() < rows_scratch(E, rc):
-            self._rows = torch.empty(rows_scratch(E, rc), dtype=torch.int32, device="cuda")
-        ptr = {}
-        for name in ("view", "feature", "group_num", "mean_action", "actions"):
-            p, nb = _P(), ctypes.c_size_t()
-            eng._check(eng._dll.mfx_battle_rollout_buffer(eng.game, name.encode(), group if name in ("view", "feature")
-                                                          else 0, ctypes.byref(p), ctypes.byref(nb)), "rollout_buffer")
-            ptr[name] = p
+        ptr, rows, total = _rollout_args(self._rows, eng, group,
+                                         ("view", "feature", "group_num", "mean_action", "actions"))
         if prob_rows is not None:
             if (prob_rows.dtype != torch.float32 or not prob_rows.is_cuda or not prob_rows.is_contiguous()
                     or tuple(prob_rows.shape) != (E, rc, self.A)):
                 raise ValueError("QNetHIP.act_rollout: prob_rows must be a contiguous float32 CUDA tensor [%d, %d, %d], "
                                  "got %s %s" % (E, rc, self.A, prob_rows.dtype, tuple(prob_rows.shape)))
-            args = (self.handle, ptr["view"], ptr["feature"], ptr["group_num"], _ptr(prob_rows), int(E), int(G),
-                    int(group), int(rc), _P(self._rows.data_ptr()), _P(self._rows.data_ptr() + 4 * E * rc), ptr["actions"])
-            if temperature is not None:
-                check(self._L.mfx_qnet_act_rollout_rows_sample(
-                    *args, ctypes.c_float(temperature), ctypes.c_uint32(seed & 0xFFFFFFFF),
-                    ctypes.c_uint32(step & 0xFFFFFFFF), _P(eng.stream_handle())), "mfx_qnet_act_rollout_rows_sample")
-            else:
-                check(self._L.mfx_qnet_act_rollout_rows(*args, _P(eng.stream_handle())), "mfx_qnet_act_rollout_rows")
-            return
-        stride = eng.mean_stride()
+            prob = (_ptr(prob_rows),)
+        else:
+            prob = (ptr["mean_action"], int(eng.mean_stride()))
+        args = (self.handle, ptr["view"], ptr["feature"], ptr["group_num"], *prob, int(E), int(G), int(group), int(rc),
+                rows, total, ptr["actions"])
         if temperature is not None:
-            check(self._L.mfx_qnet_act_rollout_sample(
-                self.handle, ptr["view"], ptr["feature"], ptr["group_num"], ptr["mean_action"], int(stride), int(E),
-                int(G), int(group), int(rc), _P(self._rows.data_ptr()), _P(self._rows.data_ptr() + 4 * E * rc),
-                ptr["actions"], ctypes.c_float(temperature), ctypes.c_uint32(seed & 0xFFFFFFFF),
-                ctypes.c_uint32(step & 0xFFFFFFFF), _P(eng.stream_handle())), "mfx_qnet_act_rollout_sample")
-            return
-        check(self._L.mfx_qnet_act_rollout(self.handle, ptr["view"], ptr["feature"], ptr["group_num"],
-                                           ptr["mean_action"], int(stride), int(E), int(G), int(group), int(rc),
-                                           _P(self._rows.data_ptr()), _P(self._rows.data_ptr() + 4 * E * rc),
-                                           ptr["actions"], _P(eng.stream_handle())), "mfx_qnet_act_rollout")
+            args += (ctypes.c_float(temperature), _u32(seed), _u32(step))
+        fn = {(False, False): "mfx_qnet_act_rollout", (False, True): "mfx_qnet_act_rollout_sample",
+              (True, False): "mfx_qnet_act_rollout_rows", (True, True): "mfx_qnet_act_rollout_rows_sample"}[
+                  (prob_rows is not None, temperature is not None)]
+        check(getattr(self._L, fn)(*args, _P(eng.stream_handle())), fn)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -483,7 +490,7 @@ class ACNetHIP:
         val = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
         act = torch.empty(n, dtype=torch.int32, device=dev) if want_act else None
         check(self._L.mfx_acnet_forward(self.handle, _ptr(view), _ptr(feature), _ptr(prob), int(n), _ptr(pol), _ptr(val),
-                                        _ptr(act), ctypes.c_uint32(seed & 0xFFFFFFFF), ctypes.c_uint32(step & 0xFFFFFFFF),
+                                        _ptr(act), _u32(seed), _u32(step),
                                         _stream()), "mfx_acnet_forward")
         return pol, val, act
 
@@ -503,17 +510,7 @@ class ACNetHIP:
                 self.set_input_support(m)
         elif self._support is not None:
             self.set_input_support(None)
-        rows = self._rows.get(id(eng))
-        if rows is None or rows.numel() < rows_scratch(E, rc):
-            rows = self._rows[id(eng)] = torch.empty(rows_scratch(E, rc), dtype=torch.int32, device="cuda")
-        ptr = {}
-        for name in ("view", "feature", "group_num", "actions"):
-            p, nb = _P(), ctypes.c_size_t()
-            eng._check(eng._dll.mfx_battle_rollout_buffer(eng.game, name.encode(), group if name in ("view", "feature")
-                                                          else 0, ctypes.byref(p), ctypes.byref(nb)), "rollout_buffer")
-            ptr[name] = p
+        ptr, rows, total = _rollout_args(self._rows, eng, group, ("view", "feature", "group_num", "actions"))
         check(self._L.mfx_acnet_act_rollout(self.handle, ptr["view"], ptr["feature"], ptr["group_num"], int(E), int(G),
-                                            int(group), int(rc), _P(rows.data_ptr()),
-                                            _P(rows.data_ptr() + 4 * E * rc), ptr["actions"],
-                                            ctypes.c_uint32(seed & 0xFFFFFFFF), ctypes.c_uint32(step & 0xFFFFFFFF),
+                                            int(group), int(rc), rows, total, ptr["actions"], _u32(seed), _u32(step),
                                             _P(eng.stream_handle())), "mfx_acnet_act_rollout")

@@ -434,3 +434,151 @@ def test_rollout_rows_match_numpy(E):
     want = np.concatenate([e * rowcap + np.arange(k) for e, k in enumerate(n)]) if n.sum() else np.zeros(0, np.int32)
     assert got[E * rowcap] == n.sum()
     assert np.array_equal(got[:len(want)], want)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# a forward needs weights; one network serves engines on several streams
+# ---------------------------------------------------------------------------------------------------------------
+def _small_engine(E, steps=0, stream=None):
+    """E envs of 64x64 on `stream` (None: the current one) with a current observation in the rollout buffers."""
+    import torch
+    from mfrl_amd.battle import BattleBatch
+    left, right = bd.block_positions(64, 128)
+    eng = BattleBatch(64, E, stream=stream if stream is not None else torch.cuda.current_stream())
+    eng.rollout_init([left, right], max_steps=400, eps=0.2, seed=5, stagger=True)
+    if steps:
+        eng.rollout_step(steps)
+    eng.rollout_policy_observe()
+    eng.sync()
+    return eng
+
+
+def _actions(eng):
+    import torch
+    act = torch.empty((eng.n_envs, 2, eng.rowcap), dtype=torch.int32, device="cuda")
+    eng.rollout_copy("actions", act)
+    eng.sync()
+    return act
+
+
+def _refused(call):
+    """`call` raises and mfx_last_error names the rule."""
+    from mfrl_amd import EngineError, lib
+    with pytest.raises(EngineError, match="needs weights"):
+        call()
+    assert "needs weights" in lib().mfx_last_error().decode()
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+def test_forward_before_weights_is_refused(precision):
+    """A QNetHIP / ACNetHIP without load(): forward on one row and the C-level act_rollout on an engine of 1 env are
+    refused ("needs weights"), in f32 and after the switch to bf16, and leave the action buffer alone.  After load
+    the same calls succeed.  In f32 they match the torch module within this file's 1e-5.  In bf16 they are NOT compared
+    with the module here: they are bit for bit those of a handle that was born in bf16 and loaded, and it is
+    tests/test_policy_bf16_gpu.py and tests/test_acnet_bf16_gpu.py that hold such a handle to its reference.
+    act_rollout writes the dense forward's actions."""
+    import ctypes
+    import torch
+    from mfrl_amd import check
+    from mfrl_amd.policy import ACNetHIP, QNetHIP
+    view, feat, prob = (x[:1].contiguous() for x in _rollout_obs(E=4, steps=5))
+    eng = _small_engine(1)
+    E, rc = 1, eng.rowcap
+    qnet, acnet = _net(True, 3), _acnet(False, 4)
+    q, ac = QNetHIP((13, 13, 7), (34,), 21, True), ACNetHIP((13, 13, 7), (34,), 21, False)
+    if precision == "bf16":
+        check(q._L.mfx_qnet_set_precision(q.handle, 1, ctypes.c_void_p()), "mfx_qnet_set_precision")
+        ac.set_precision("bf16")
+    eng.rollout_write("actions", torch.full((E, 2, rc), -7, dtype=torch.int32, device="cuda"))
+    _refused(lambda: q.forward(view, feat, prob))
+    _refused(lambda: q.forward(view, feat, prob, temperature=0.5))
+    _refused(lambda: ac.forward(view, feat))
+    _refused(lambda: q.act_rollout(eng, 0))
+    _refused(lambda: q.act_rollout(eng, 0, temperature=0.5))
+    _refused(lambda: q.act_rollout(eng, 0, prob_rows=torch.zeros((E, rc, 21), device="cuda")))
+    _refused(lambda: ac.act_rollout(eng, 0, seed=1, step=2))
+    assert bool((_actions(eng) == -7).all())
+    q.load(qnet)
+    ac.load(acnet)
+    got_q, got_a = q.forward(view, feat, prob)
+    pol, _, act = ac.forward(view, feat, seed=1, step=2)
+    if precision == "f32":
+        with torch.no_grad():
+            want_q, (want_p, _) = qnet(view, feat, prob), acnet(view, feat, None)
+        torch.cuda.synchronize()
+        assert float((got_q - want_q).abs().max()) <= 1e-5 * max(1.0, float(want_q.abs().max()))
+        assert float((pol - want_p).abs().max()) <= 1e-5
+    else:
+        born_q = QNetHIP((13, 13, 7), (34,), 21, True, precision="bf16").load(qnet)
+        born_ac = ACNetHIP((13, 13, 7), (34,), 21, False, precision="bf16").load(acnet)
+        want_q, want_a = born_q.forward(view, feat, prob)
+        want_p, _, want_act = born_ac.forward(view, feat, seed=1, step=2)
+        torch.cuda.synchronize()
+        assert torch.equal(got_q, want_q) and torch.equal(got_a, want_a)
+        assert torch.equal(pol, want_p) and torch.equal(act, want_act)
+    # the rollout calls: the dense forward's actions on the engine's own observation (group 0: Q, group 1: AC)
+    q.act_rollout(eng, 0)
+    ac.act_rollout(eng, 1, seed=1, step=2)
+    got = _actions(eng)
+    num = torch.empty((E, 2), dtype=torch.int32, device="cuda")
+    mean = torch.empty((E, 2, 21), dtype=torch.float64, device="cuda")
+    eng.rollout_copy("group_num", num)
+    eng.rollout_copy("mean_action", mean)
+    for g in range(2):
+        v = torch.empty((E, rc, 1183), dtype=torch.float32, device="cuda")
+        f = torch.empty((E, rc, 34), dtype=torch.float32, device="cuda")
+        eng.rollout_copy("view", v, group=g)
+        eng.rollout_copy("feature", f, group=g)
+        eng.sync()
+        n = int(num[0, g])
+        assert n > 0
+        if g == 0:
+            want = q.act(v[0, :n].reshape(n, 13, 13, 7), f[0, :n], mean[0, 0].float().expand(n, 21))
+        else:
+            import acnet_ref
+            p = ac.forward(v[0, :n], f[0, :n], want_act=False)[0]
+            want = torch.from_numpy(acnet_ref.draw(p.cpu().numpy(), 1, 2, 1, np.arange(n))).cuda().int()
+        torch.cuda.synchronize()
+        assert torch.equal(got[0, g, :n], want), g
+        assert bool((got[0, g, n:] == -7).all()), g
+
+
+def test_two_engines_on_two_streams_share_one_qnet():
+    """Engines of 3 and 70 envs (70: past one 64-env chunk of the row list) at 64x64, each on its own non-default
+    stream, share one QNetHIP: act_rollout issued alternately on both, with no stream context and no sync between
+    the calls, writes into each engine's action buffer what a private QNetHIP with the same weights writes for it --
+    greedy, sampled, and with a mean action per row.  What makes this hold is in the code, not in the timing: the
+    row-list scratch is kept per engine (mfrl_amd.policy._rollout_args) and the conv -> head pass buffer per stream
+    (QNetHandle::conv)."""
+    import torch
+    from mfrl_amd.policy import QNetHIP
+    net = _net(True, 9)
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    engs = [_small_engine(E, steps=20, stream=s) for E, s in zip((3, 70), streams)]
+    assert all(e.stream_handle() for e in engs) and engs[0].stream_handle() != engs[1].stream_handle()
+    shared = QNetHIP((13, 13, 7), (34,), 21, True).load(net)
+    private = [QNetHIP((13, 13, 7), (34,), 21, True).load(net) for _ in engs]
+    g = torch.Generator(device="cuda").manual_seed(3)
+    rows = [torch.rand((e.n_envs, e.rowcap, 21), device="cuda", generator=g) for e in engs]
+    rows = [(r / r.sum(2, keepdim=True)).contiguous() for r in rows]
+    blank = [torch.full((e.n_envs, 2, e.rowcap), -7, dtype=torch.int32, device="cuda") for e in engs]
+    torch.cuda.synchronize()                                   # the weights and these tensors: ready on every stream
+
+    def run(nets, **kw):
+        for e, b in zip(engs, blank):
+            e.rollout_write("actions", b)
+        for grp in range(2):
+            for k, e in enumerate(engs):                       # alternately, nothing in between
+                extra = dict(kw)
+                if extra.pop("per_row", False):
+                    extra["prob_rows"] = rows[k]
+                nets[k].act_rollout(e, grp, **extra)
+        return [_actions(e) for e in engs]
+
+    for kw in ({}, {"temperature": 0.7, "seed": 11, "step": 4}, {"per_row": True},
+               {"per_row": True, "temperature": 0.7, "seed": 11, "step": 4}):
+        got = run([shared, shared], **kw)
+        want = run(private, **kw)
+        for k in range(2):
+            assert torch.equal(got[k], want[k]), (kw, k)
+            assert int((want[k] >= 0).sum()) > 100 and len(torch.unique(want[k])) > 2, (kw, k)   # (-7 and actions)
