@@ -53,7 +53,8 @@ int env_step(void *game, int *done);
 int env_get_reward(void *game, int group, float *buffer);
 /* runtime_api.h:32 -- num, id, pos, alive, action_space, view_space, feature_space,
  * view2attack, attack_base, both_attack, global_minimap, mean_info, walls_info,
- * render_window_info, attack_event, groups_info (GridWorld.cc:777-978) */
+ * render_window_info, attack_event, groups_info (GridWorld.cc:777-978); and one name the reference lacks,
+ * move_delta: int32 [n_move][2], the (dx, dy) of move action a (the scripted opponent's table, mfx_rule_create) */
 int env_get_info(void *game, int group, const char *name, void *buffer);
 /* runtime_api.h:35-36 -- RenderGenerator's frame files: config.json + video_<n>.txt of env 0
  * (RenderGenerator.cc), byte-identical to the reference build's; only the websocket server and the
@@ -385,6 +386,44 @@ int mfx_q_sample(const float *d_q, int n, int A, float temperature, uint32_t see
                  float *d_w, int32_t *d_act, void *stream);
 int mfx_q_sample_rows(const float *d_q, const int32_t *d_rows, int n, int A, float temperature, uint32_t seed,
                       uint32_t step, int group, float *d_w, int32_t *d_act, void *stream);
+
+/* The scripted opponents "rush" and "random" of the device rollout loop (csrc/rule_kernels.hip, k_rule_act; DESIGN
+ * 7p; tests/rule_ref.py restates the rule in numpy).  The project's own deterministic rule -- not the reference's
+ * rush_prey_infer_action -- giving one action per observation row from that row alone: view [VH][VW][7] f32 as
+ * env_get_observation gives it to the observing group (0 wall, 1 own group, 3 own minimap, 4 enemy, 6 enemy minimap;
+ * both minimaps carry +1 at the agent's own bin), feature [F] f32 ending in x / W, y / H.  cy = VH / 2, cx = VW / 2;
+ * comparisons on f32 as written, arithmetic integer:
+ *   A  attack       the first row-major cell with enemy > 0.5 and view2attack >= 0: attack_base + view2attack
+ *   B  in view      else, if a cell has enemy > 0.5: the one minimising (r - cy)^2 + (c - cx)^2, first row-major on
+ *                   ties; d = (c - cx, r - cy)
+ *   C  out of view  own bin: the first row-major cell with own minimap > 1.0; D = enemy minimap, minus 1.0f at the own
+ *                   bin; target: the first row-major cell among those of the largest D > 0.  With an own bin, a target
+ *                   and target != own bin, d = 64 (sign(c - bx), sign(r - by)); else
+ *                   d = 64 (sign(0.5f - fx), sign(0.5f - fy)), fx, fy the last two features
+ *   move            a < attack_base is free if move[a] == (0, 0), or if (cy + my, cx + mx) is inside the view with
+ *                   wall, own and enemy all <= 0.5; the free a minimising (dx - mx)^2 + (dy - my)^2, first index on
+ *                   ties (0 if none is free)
+ *   exploration     u1 = the actor-critic draw's uniform (seed, step, group, row); u1 < eps: the action is
+ *                   min(int(u2 * n_action), n_action - 1), u2 = the uniform (seed ^ 0x68E31DA4, step, group, row), one
+ *                   f32 multiply.  eps = 0 never draws; eps = 1 is the random opponent.
+ * mfx_rule_create: shape = {view_h, view_w, channels, feature}; view2attack int32 [view_h][view_w]; move_dx, move_dy
+ * int32 [attack_base] (env_get_info "move_delta").  Pure data -- no game pointer, no device memory -- so one handle
+ * serves the drop-in env and a rollout batch.  Supported: 7 channels (two groups, minimap on, no food mode), no turn
+ * mode (attack_base = the number of moves), view_h * view_w <= 256, 2 <= n_action <= 64, feature >= 2, moves within
+ * 16 cells; anything else returns -1.
+ * mfx_rule_act: n dense rows -> d_act [n], row i drawn with (seed, step, group, i).  mfx_rule_act_rollout: group g of
+ * a rollout batch, the argument conventions of mfx_qnet_act_rollout_sample (d_rows: E * rowcap ints, d_total: 1 +
+ * ceil(E / 64) ints); row j of env e drawn with (seed, step, g, e * rowcap + j); only the action slots of live rows
+ * are written.  A null pointer, n < 0 or an eps outside [0, 1] (NaN included) returns -1 before anything is
+ * launched. */
+int mfx_rule_create(const int32_t *shape, int attack_base, int n_action, const int32_t *view2attack,
+                    const int32_t *move_dx, const int32_t *move_dy, void **handle);
+int mfx_rule_destroy(void *handle);
+int mfx_rule_act(void *handle, const float *d_view, const float *d_feat, int n, float eps, uint32_t seed,
+                 uint32_t step, int group, int32_t *d_act, void *stream);
+int mfx_rule_act_rollout(void *handle, const float *d_view, const float *d_feat, const int32_t *d_counts, int E, int G,
+                         int g, int rowcap, int32_t *d_rows, int32_t *d_total, int32_t *d_act, float eps, uint32_t seed,
+                         uint32_t step, void *stream);
 
 /* The compact row list the act_rollout calls build: d_rows[i] = e * rowcap + j over envs e, j < min(counts[e][g],
  * rowcap), in env order; d_total[0] = the row count (d_total: 1 + ceil(E / 64) ints). */

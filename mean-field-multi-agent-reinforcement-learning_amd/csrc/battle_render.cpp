@@ -23,6 +23,10 @@ int BattleEngine::get_info(int group, const char* name, void* buf) {   // GridWo
             ib[(t.attack.dy[i] - t.view.y1) * t.view.w + (t.attack.dx[i] - t.view.x1)] = i;
         return 0;
     }
+    if (!strcmp(name, "move_delta")) {                           // (not in the reference: mfx_rule_create's move table)
+        for (int i = 0; i < t.move.count; i++) { ib[2 * i] = t.move.dx[i]; ib[2 * i + 1] = t.move.dy[i]; }
+        return 0;
+    }
     if (!strcmp(name, "both_attack")) { ib[0] = 0; return 0; }   // statistics are compiled off (GridWorld.cc:501)
     if (!strcmp(name, "mean_info")) return mean_info(group, (float*)buf);
     return fail("unsupported info name in get_info: %s", name);

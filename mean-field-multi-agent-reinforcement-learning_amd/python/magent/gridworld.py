@@ -50,6 +50,7 @@ class GridWorld(Environment):
             except ImportError:
                 raise BaseException('unknown built-in game "%s"' % config)
             config = mod.get_config(**kwargs)
+        self._config = config                # (read back by code that supports some configs only: mfrl_amd.algo.rule)
         self._lib = lib if lib is not None else get_lib()
         L = self._lib
 
@@ -292,6 +293,16 @@ class GridWorld(Environment):
         base = ctypes.c_int32()
         self._lib.env_get_info(self.game, _hv(handle), b"attack_base", ctypes.byref(base))
         return base.value, buf
+
+    def get_move_delta(self, handle):
+        """int32 [n_move, 2]: the (dx, dy) of every move action of the group's type, in action order (env_get_info
+        "move_delta", a name this engine adds: the scripted opponent's table, mfrl_amd.algo.rule)."""
+        base = ctypes.c_int32()
+        self._lib.env_get_info(self.game, _hv(handle), b"attack_base", ctypes.byref(base))
+        # (one row per action below attack_base: the moves, and in turn mode the two turns, which stay (0, 0))
+        buf = np.zeros((base.value, 2), dtype=np.int32)
+        self._lib.env_get_info(self.game, _hv(handle), b"move_delta", buf.ctypes.data_as(ctypes.c_void_p))
+        return buf
 
     def set_seed(self, seed):
         self._lib.env_config_game(self.game, b"seed", ctypes.byref(ctypes.c_int(seed)))

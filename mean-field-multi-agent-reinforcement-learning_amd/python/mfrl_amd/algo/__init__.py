@@ -22,6 +22,9 @@ def spawn_ai(algo_name, sess, env, handle, human_name, max_steps, memory_size=80
         model = AC(sess, human_name, handle, env)
     elif algo_name == "il":
         model = IL(sess, human_name, handle, env, max_steps, memory_size=memory_size)
+    elif algo_name in ("rush", "random"):       # the scripted opponents (algo/rule.py): no network, nothing to train
+        from .rule import RulePolicy
+        model = RulePolicy(sess, human_name, handle, env, rule=algo_name)
     else:
         raise ValueError("unknown algo %r" % algo_name)
     return model

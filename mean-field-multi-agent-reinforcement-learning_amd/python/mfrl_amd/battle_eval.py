@@ -6,6 +6,8 @@ algorithms, play --n_round evaluation rounds; the last line is the reference's W
     python -m mfrl_amd.battle_eval --algo mfac --oppo ac --envs 8192 --act_precision bf16 --idx 1999 1999
     python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --watch 0 63 --idx 1999 1999    # + frames of two envs
     python -m mfrl_amd.battle_eval --algo mfq --oppo mfac --envs 64 --explore boltzmann --temperature 0.1 --idx 1999 1999
+    python -m mfrl_amd.battle_eval --algo mfq --oppo rush --envs 64 --idx 1999      # against the scripted rush opponent
+    python -m mfrl_amd.battle_eval --algo rush --oppo random --envs 64               # two scripted sides: nothing loaded
 
 Models are loaded from <base_dir>/data/models/<algo>-0 and <base_dir>/data/models/<oppo>-1 at the two --idx steps, as
 the reference does (train_battle saves them there).  --envs 1 is the reference's path unchanged: tools.Runner with
@@ -15,6 +17,10 @@ mfrl_amd.scoreboard.RolloutScoreboard with Runner.run's own win rule -- kill[i] 
 before clear_dead; a tie counts for both sides --, so WIN_RATE is over n_round * E episodes.  --watch ENV [ENV ...]
 records those envs of the first --watch_rounds rounds on the device (mfrl_amd.recorder), re-runs each one's first episode
 on the one-env engine and writes the reference's frame files under <render dir>/round_<k>/env_<e>/.
+
+--algo / --oppo also take the scripted opponents rush and random (mfrl_amd.algo.rule): a fixed yardstick
+that loads nothing, so --idx then takes one value per learned side, in order (two, one or none).  --rule_eps is the
+share of uniform actions a rush side mixes in (default 0).
 """
 import argparse
 import math
@@ -29,17 +35,21 @@ from .algo import spawn_ai, tools
 from .algo.play import battle, battle_rollout
 
 ALGOS = ("ac", "mfac", "mfq", "il")
+RULES = ("rush", "random")          # the scripted opponents (mfrl_amd.algo.rule): nothing to load
 
 
 def main(argv=None):
     parser = argparse.ArgumentParser()
-    parser.add_argument("--algo", type=str, choices=ALGOS, required=True, help="the main model's algorithm")
-    parser.add_argument("--oppo", type=str, choices=ALGOS, help="the opponent model's algorithm (default: --algo)")
+    parser.add_argument("--algo", type=str, choices=ALGOS + RULES, required=True,
+                        help="the main model's algorithm, or a scripted opponent (rush, random)")
+    parser.add_argument("--oppo", type=str, choices=ALGOS + RULES,
+                        help="the opponent model's algorithm or scripted opponent (default: --algo)")
     parser.add_argument("--n_round", type=int, default=50)
     parser.add_argument("--render", action="store_true")
     parser.add_argument("--map_size", type=int, default=40)
     parser.add_argument("--max_steps", type=int, default=400)
-    parser.add_argument("--idx", nargs="*", help="the saved steps of the two models: A B")
+    parser.add_argument("--idx", nargs="*", help="the saved steps of the learned models, one per learned side in order: "
+                                                 "A B (a rush / random side loads nothing)")
     parser.add_argument("--envs", type=int, default=1, help="envs per round (>1: the device rollout loop)")
     parser.add_argument("--act_precision", type=str, choices=["f32", "bf16"], default="f32",
                         help="the acting forward's matrix operands on the device rollout loop (mfrl_amd.policy)")
@@ -61,9 +71,19 @@ def main(argv=None):
                              "-- group (the reference) or neighbors (the agents of the group within --mf_radius cells)")
     parser.add_argument("--mf_radius", type=int, default=None,
                         help="with --mean_field neighbors: the Chebyshev radius, >= 0 (default 6, the view's)")
+    parser.add_argument("--rule_eps", type=float, default=None,
+                        help="with a rush side: the probability of a uniform action instead of the rule's, in [0, 1] "
+                             "(default 0)")
     args = parser.parse_args(argv)
     if args.oppo is None:
         args.oppo = args.algo
+    learned = [i for i, a in enumerate((args.algo, args.oppo)) if a not in RULES]
+    if args.rule_eps is not None:
+        if "rush" not in (args.algo, args.oppo):
+            parser.error("--rule_eps is the exploration of a rush side: neither --algo nor --oppo is rush (random is "
+                         "eps = 1)")
+        if not 0.0 <= args.rule_eps <= 1.0:
+            parser.error("--rule_eps must be in [0, 1]")
     if args.mean_field != "group":
         if args.algo not in ("mfq", "mfac") and args.oppo not in ("mfq", "mfac"):
             parser.error("--mean_field neighbors is the mean action of a mean-field model: neither --algo nor --oppo is "
@@ -92,8 +112,12 @@ def main(argv=None):
         parser.error("--max_steps must be at least 1")
     if args.untrained and args.idx:
         parser.error("--untrained loads nothing: give it or --idx A B, not both")
-    if not args.untrained and (args.idx is None or len(args.idx) != 2):
-        parser.error("--idx takes the two saved steps A B (or give --untrained)")
+    if len(learned) == 2:
+        if not args.untrained and (args.idx is None or len(args.idx) != 2):
+            parser.error("--idx takes the two saved steps A B (or give --untrained)")
+    elif not args.untrained and len(args.idx or []) != len(learned):
+        parser.error("--idx takes one saved step per learned side: {} here ({} vs {}; rush / random load nothing), or "
+                     "give --untrained".format(len(learned), args.algo, args.oppo))
     if args.render and args.envs > 1:
         parser.error("--render draws one env through the drop-in API: --envs 1")
     if args.act_precision != "f32" and args.envs <= 1:
@@ -125,8 +149,12 @@ def main(argv=None):
     models = [spawn_ai(args.algo, None, env, handles[0], args.algo + "-me", args.max_steps, memory_size=1024),
               spawn_ai(args.oppo, None, env, handles[1], args.oppo + "-opponent", args.max_steps, memory_size=1024)]
     if not args.untrained:
-        models[0].load(main_model_dir, step=args.idx[0])
-        models[1].load(oppo_model_dir, step=args.idx[1])
+        for i, step in zip(learned, args.idx or []):      # (a rule side loads nothing)
+            models[i].load((main_model_dir, oppo_model_dir)[i], step=step)
+    if args.rule_eps is not None:
+        for m in models:
+            if getattr(m, "rule", None) == "rush":
+                m.eps = args.rule_eps
     for m in models:
         if args.explore != "greedy" and hasattr(type(m), "explore"):     # (the Q models of the pairing)
             m.explore = args.explore

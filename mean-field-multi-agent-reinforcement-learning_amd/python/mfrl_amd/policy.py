@@ -35,6 +35,9 @@ then moves by about 1e-2 at most (the division by 0.1 amplifies the error; tests
 sampling policy tolerates and a bootstrap value would not: forward(want_value=True) raises in this mode, and the
 input support, which the f32 kernel uses bit-identically, is not used.  The contract is restated in numpy in
 tests/acnet_bf16_ref.py.
+
+RuleHIP (at the end): the scripted rush / random opponent on csrc/rule_kernels.hip -- no network, one action per
+observation row; the rule is restated in numpy in tests/rule_ref.py.
 """
 import ctypes
 
@@ -514,3 +517,71 @@ class ACNetHIP:
         check(self._L.mfx_acnet_act_rollout(self.handle, ptr["view"], ptr["feature"], ptr["group_num"], int(E), int(G),
                                             int(group), int(rc), rows, total, ptr["actions"], _u32(seed), _u32(step),
                                             _P(eng.stream_handle())), "mfx_acnet_act_rollout")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the scripted opponents "rush" / "random" (mfrl_amd.algo.rule) on csrc/rule_kernels.hip
+# ---------------------------------------------------------------------------------------------------------------
+class RuleHIP:
+    """The scripted rule of csrc/rule_kernels.hip (k_rule_act; restated in tests/rule_ref.py): one action
+    per observation row from that row alone -- attack the first attackable enemy, else step toward the nearest enemy
+    in view, else toward the densest enemy bin of the minimap, else toward the map's centre; with probability eps a
+    uniform action.  The handle is pure data (the type's view2attack and move tables), made on the host: constructing
+    one needs no GPU, and one handle serves the host loops (act) and every rollout plan that takes a learned policy
+    (act_rollout)."""
+
+    def __init__(self, view_space, feature_space, num_actions, attack_base, view2attack, move_delta):
+        h, w, c = (int(x) for x in view_space)
+        self.view_space, self.V = (h, w, c), h * w * c
+        self.F, self.A = int(feature_space[0]), int(num_actions)
+        L = lib()
+        for fn in ("mfx_rule_create", "mfx_rule_destroy", "mfx_rule_act", "mfx_rule_act_rollout"):
+            getattr(L, fn).restype = ctypes.c_int
+        self._L = L
+        v2a = np.ascontiguousarray(np.asarray(view2attack, dtype=np.int32).reshape(-1))
+        mv = np.asarray(move_delta, dtype=np.int32).reshape(-1, 2)
+        if v2a.size != h * w:
+            raise ValueError("RuleHIP: view2attack has %d cells, the view %d x %d" % (v2a.size, h, w))
+        if len(mv) != int(attack_base):
+            raise ValueError("RuleHIP: %d moves, attack_base %d (turn mode is not supported)" % (len(mv), attack_base))
+        dx, dy = np.ascontiguousarray(mv[:, 0]), np.ascontiguousarray(mv[:, 1])
+        shape = (ctypes.c_int32 * 4)(h, w, c, self.F)
+        as_i32 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))     # noqa: E731
+        hdl = _P()
+        check(L.mfx_rule_create(shape, int(attack_base), self.A, as_i32(v2a), as_i32(dx), as_i32(dy), ctypes.byref(hdl)),
+              "mfx_rule_create")
+        self.handle = hdl
+        self._rows = {}
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self._L.mfx_rule_destroy(self.handle)
+            self.handle = None
+
+    def act(self, view, feature, eps=0.0, seed=0, step=0, group=0):
+        """view [n, VH, VW, 7], feature [n, F] float32 CUDA tensors -> actions [n] int32; row i's exploration draw
+        uses the uniform (seed, step, group, i).  An eps outside [0, 1] raises (nothing is launched)."""
+        n = view.shape[0]
+        if view.numel() != n * self.V or feature.numel() != n * self.F:
+            raise ValueError("RuleHIP.act: %d rows of %s view and %s feature floats, the handle takes %d and %d"
+                             % (n, tuple(view.shape[1:]), tuple(feature.shape[1:]), self.V, self.F))
+        view = view.reshape(n, self.V).contiguous().float()
+        feature = feature.reshape(n, self.F).contiguous().float()
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError("RuleHIP.act: eps must be in [0, 1], got %r" % (eps,))
+        act = torch.empty(n, dtype=torch.int32, device=view.device)
+        if n:
+            check(self._L.mfx_rule_act(self.handle, _ptr(view), _ptr(feature), int(n), ctypes.c_float(eps), _u32(seed),
+                                       _u32(step), int(group), _ptr(act), _stream()), "mfx_rule_act")
+        return act
+
+    def act_rollout(self, eng, group, eps=0.0, seed=0, step=0):
+        """Actions of group `group` of a BattleBatch rollout from its current observation buffers, written into the
+        rollout's action buffer [E][G][rowcap] (live rows only; row j of env e drawn with (seed, step, group,
+        e * rowcap + j)).  Nothing is read back.  Runs on every plan that takes a learned policy; the row-list scratch
+        is per engine."""
+        E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
+        ptr, rows, total = _rollout_args(self._rows, eng, group, ("view", "feature", "group_num", "actions"))
+        check(self._L.mfx_rule_act_rollout(self.handle, ptr["view"], ptr["feature"], ptr["group_num"], int(E), int(G),
+                                           int(group), int(rc), rows, total, ptr["actions"], ctypes.c_float(eps),
+                                           _u32(seed), _u32(step), _P(eng.stream_handle())), "mfx_rule_act_rollout")

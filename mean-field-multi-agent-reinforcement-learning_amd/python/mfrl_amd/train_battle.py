@@ -10,6 +10,7 @@
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann ...   # sample from softmax(q / eps)
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann --target boltzmann ...   # + the paper's v^MF target
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --mean_field neighbors --mf_radius 6 ...   # the paper's neighbourhood mean action
+    python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --eval_every 10 --eval_oppo rush ...   # + a round against the scripted opponent, logged to data/eval_<algo>.jsonl
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
 mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a BattleBatch (--envs).
@@ -83,7 +84,29 @@ def main(argv=None):
                              "the agents of its group within --mf_radius cells of it)")
     parser.add_argument("--mf_radius", type=int, default=None,
                         help="with --mean_field neighbors: the Chebyshev radius, >= 0 (default 6, the view's)")
+    parser.add_argument("--eval_every", type=int, default=0,
+                        help="after every K-th round play one evaluation round of the main model against a scripted "
+                             "opponent on the device rollout loop and log the outcome (0: off)")
+    parser.add_argument("--eval_oppo", type=str, choices=["rush", "random"], default=None,
+                        help="with --eval_every: the scripted opponent (mfrl_amd.algo.rule; default rush)")
+    parser.add_argument("--eval_envs", type=int, default=64, help="with --eval_every: envs (episodes) per evaluation round")
+    parser.add_argument("--eval_eps", type=float, default=None,
+                        help="with --eval_every and the rush opponent: its share of uniform actions, in [0, 1] (default 0)")
     args = parser.parse_args(argv)
+    if args.eval_every < 0:
+        parser.error("--eval_every must be >= 0")
+    if args.eval_every == 0:
+        if args.eval_oppo is not None or args.eval_eps is not None:
+            parser.error("--eval_oppo / --eval_eps describe the evaluation rounds: give --eval_every K too")
+    else:
+        args.eval_oppo = args.eval_oppo or "rush"
+        if args.eval_envs < 1:
+            parser.error("--eval_envs must be at least 1")
+        if args.eval_eps is not None:
+            if args.eval_oppo != "rush":
+                parser.error("--eval_eps is the exploration of the rush opponent (random is eps = 1)")
+            if not 0.0 <= args.eval_eps <= 1.0:
+                parser.error("--eval_eps must be in [0, 1]")
     if args.mean_field != "group":
         if args.algo not in ("mfq", "mfac"):
             parser.error("--mean_field neighbors is the mean action of a mean-field model: --algo mfq or mfac (ac / il "
@@ -182,12 +205,58 @@ def main(argv=None):
     runner = tools.Runner(None, env, handles, args.map_size, args.max_steps, models, play_handle,
                           render_every=args.save_every if args.render else 0, save_every=args.save_every, tau=0.01,
                           log_name=args.algo, log_dir=log_dir, model_dir=model_dir, train=True)
+    evaluate = _evaluator(args, env, handles, models[0]) if args.eval_every else None
     for k in range(args.n_round):
         eps = linear_decay(k, [0, int(args.n_round * 0.8), args.n_round], [1, 0.2, 0.1])
         t0 = time.time()
         runner.run(eps, k)
         torch.cuda.synchronize()
         print("[TIME] round {}: {:.2f} s ({} envs)".format(k, time.time() - t0, args.envs))
+        if evaluate is not None and (k + 1) % args.eval_every == 0:
+            evaluate(k)
+
+
+def _evaluator(args, env, handles, model):
+    """--eval_every: evaluate(k) plays one battle_rollout round of `model` (group 0) against the scripted opponent on
+    its own BattleBatch and scoreboard (made once here), prints the [EVAL] line and appends it as JSON to
+    <base_dir>/data/eval_<algo>.jsonl.  The model acts as battle_eval's default does -- the Q models greedily, the
+    actor-critic ones sampling -- and is left as it was: its explore, temperature and draw counter are restored, no
+    host random stream is consumed (left_id is k % 2), and nothing is trained or collected."""
+    import json
+
+    from .algo.play import battle_rollout
+    from .battle import BattleBatch
+    from .scoreboard import RolloutScoreboard
+    oppo = spawn_ai(args.eval_oppo, None, env, handles[1], "eval-" + args.eval_oppo, args.max_steps)
+    if args.eval_eps is not None:
+        oppo.eps = args.eval_eps
+    eng = BattleBatch(args.map_size, args.eval_envs, stream=torch.cuda.current_stream())
+    board = RolloutScoreboard(eng, ep_cap=1, target=1)
+    path = os.path.join(args.base_dir, "data", "eval_{}.jsonl".format(args.algo))
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    kept = [a for a in ("explore", "temperature", "_draws") if hasattr(model, a)]
+
+    def evaluate(k):
+        saved = {a: getattr(model, a) for a in kept}
+        try:
+            if "explore" in saved:
+                model.explore = "greedy"
+            first = battle_rollout(eng, k, args.map_size, args.max_steps, [model, oppo], eps=0.0, left_id=k % 2,
+                                   board=board)[4]["first"]
+        finally:
+            for a, v in saved.items():
+                setattr(model, a, v)
+        E = args.eval_envs
+        rec = {"round": k, "oppo": args.eval_oppo, "envs": E,
+               "win_rate": [(first["main_wins"] + first["ties"]) / E, (first["oppo_wins"] + first["ties"]) / E],
+               "kills": first["kills"], "steps": first["steps"]}
+        print("[EVAL] round {} vs {}: WIN_RATE {} / {}, kills {} / {}".format(k, args.eval_oppo, rec["win_rate"][0],
+                                                                             rec["win_rate"][1], rec["kills"][0],
+                                                                             rec["kills"][1]))
+        with open(path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+    return evaluate
 
 
 if __name__ == "__main__":
