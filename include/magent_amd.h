@@ -564,6 +564,33 @@ int mfx_collect_links_reset(int64_t *d_last, int64_t n, void *stream);
 int mfx_chain_returns(float *d_rew, const int64_t *d_prev, const int64_t *d_tails, const float *d_value,
                       int64_t n_tails, int64_t n_rows, double gamma, int numpy1, void *stream);
 
+/* GAE(lambda) advantages along the same chains (csrc/gae_kernels.hip; opt-in; tests/gae_ref.py restates it).
+ *   mfx_chain_gae      d_value_rows: one f32 value V[r] per row, [n_rows]; d_adv: [n_rows], not d_rew.  For tail i with
+ *                      t = d_tails[i], along r = t, d_prev[r], ... to -1, with x = d_rew[r] read before it is overwritten:
+ *                          nxt = (double)V[t];  g = 0.0
+ *                          per row r:  v = (double)V[r]
+ *                                      delta = ((double)x + gamma * nxt) - v
+ *                                      g     = delta + gl * g              (gl = gamma * lambda, formed once on the host)
+ *                                      d_adv[r] = (float)g;  d_rew[r] = (float)(g + v);  nxt = v
+ *                      every operation a rounded double operation of its own (no contraction).  The tail convention is the
+ *                      reference's: the value of a chain's last row stands for the state after it, as mfx_chain_returns'
+ *                      keep does, so lambda = 1 leaves the reference's bootstrapped return in d_rew and d_adv = return - V,
+ *                      and lambda = 0 the one-step TD error in d_adv.  Rows that are on no chain keep both columns.
+ *                      gamma and lambda must lie in [0, 1] (NaN is refused), before any launch.  The guards are
+ *                      mfx_chain_returns': a tail outside [0, n_rows) or a predecessor outside [0, its row) ends that walk
+ *                      before any further load or store, in either column, and the call returns -1 with the index in the
+ *                      message (it synchronises `stream` to report it; the error word is this call's own and is cleared).
+ *   mfx_adv_normalize  d_adv[0, n) <- (float)(((double)d_adv[r] - mean) / (std + 1e-8)), mean and the population standard
+ *                      deviation in double, two passes.  One summation order per n: workgroup b sums elements [b span,
+ *                      (b + 1) span) -- span = ceil(n / min(ceil(n / 4096), 1024)) -- each thread its elements t, t + 256,
+ *                      ... in order, the threads by a fixed tree; then the workgroups' partials in index order.  No
+ *                      floating-point atomics: equal input gives bitwise equal output.  n = 1 or a constant column gives
+ *                      all zeros (exactly, while n < 2^29).  n = 0 does nothing.  Nothing is read back.  The scratch is
+ *                      the library's: two calls must not run at once on two streams of a device. */
+int mfx_chain_gae(float *d_rew, float *d_adv, const int64_t *d_prev, const int64_t *d_tails, const float *d_value_rows,
+                  int64_t n_tails, int64_t n_rows, double gamma, double lambda, void *stream);
+int mfx_adv_normalize(float *d_adv, int64_t n, void *stream);
+
 /* ---------------------------------------------------------------- part 7: episode outcomes (csrc/score_kernels.hip) */
 /* The scorekeeper of the device rollout loop: per-episode outcomes of every env with Runner.run's own win rule
  * (algo/tools.py, train=False), with no host work per step.  Group 0 is "main", group 1 "opponent"; two groups only
@@ -783,7 +810,12 @@ int mfx_qtrain_error(void *handle, int *code, long long *bad_value, void *stream
  *   set_chunk_rows   rows per chunk, 1 .. 262144 (0: the default, 12288 -- 137 MB of scratch for the kept activations
  *                    and the backward intermediates at 11 KB per row, plus 24 partial gradient blobs).  Each chunk's
  *                    weight-gradient partials are added into the gradient blob in chunk order.
- *   grads            the gradient in blob layout (padding exactly zero) into d_grad_blob and (pg_loss, vf_loss, ent_loss,
+ *   set_advantage    d_adv: a float32 column of n rows, or null (the default).  Host state, read by the grads / step
+ *                    calls that follow: with a column, adv of the policy term is d_adv[i] (mfx_chain_gae's, opt-in,
+ *                    DESIGN 7q) where the default forms ret - v; the value term and dL/dv use ret - v either way, ret
+ *                    being the reward column after the walk.  The column must stay valid until those calls have run.
+ *                    Null restores the default, bit for bit a fresh handle's.  mfx_actrain_rows is unchanged.
+ *   grads           the gradient in blob layout (padding exactly zero) into d_grad_blob and (pg_loss, vf_loss, ent_loss,
  *                    mean value) -- vf_loss and ent_loss with their coefficients, as ActorCritic.train prints them -- into
  *                    d_stats (either may be null); no state changes; bit for bit the gradient step applies
  *   step             grads, then Adam (bias-corrected from the step count), enqueued by this one call; nothing is read
@@ -814,6 +846,7 @@ int mfx_actrain_reset_optimizer(void *handle, void *stream);
 int mfx_actrain_step_count(void *handle, long long *t);
 int mfx_actrain_set_input_support(void *handle, const uint8_t *mask, int n, void *stream);
 int mfx_actrain_set_chunk_rows(void *handle, int chunk_rows);
+int mfx_actrain_set_advantage(void *handle, const float *d_adv);
 int mfx_actrain_grads(void *handle, const mfx_actrain_rows *rows, long long n, float *d_grad_blob, float *d_stats,
                       void *stream);
 int mfx_actrain_step(void *handle, const mfx_actrain_rows *rows, long long n, float *d_stats, void *stream);

@@ -185,6 +185,9 @@ __global__ void __launch_bounds__(256) k_at_gemm(GemmArgs g) {
 // Row i: z -> s = softmax, p = clamp(s, 1e-10f, 1 - 1e-10f), lp = log(p + 1e-6f); the stats' terms; dL/dz over z in
 // place (columns past A: 0) and dL/dv.  The action is checked before it selects anything; a bad one sets the sticky
 // error word (the first wins) and the row goes on with action 0 -- k_at_adam then applies nothing.
+// ADV (mfx_actrain_set_advantage): the policy term's advantage is read from the column advcol instead of
+// being formed as R - v; the value term and dL/dv use R - v either way.  ADV = false is the reference's head, its code
+// untouched by the other instantiation (profiles/gae_resources.txt).
 struct LossArgs {
     float* Z;                 // [rows][32]
     const float* val;
@@ -197,7 +200,8 @@ struct LossArgs {
     float n_rows, value_coef, ent_coef;  // n_rows: all rows of the step (the means' divisor)
 };
 
-__global__ void __launch_bounds__(256) k_at_loss(LossArgs a) {
+template <bool ADV>
+__global__ void __launch_bounds__(256) k_at_loss(LossArgs a, const float* __restrict__ advcol) {
     __shared__ float red[4][256];
     __shared__ float sk[32][256];                        // the row's softmax, one column per thread
     const int tid = threadIdx.x, i = blockIdx.x * 256 + tid;
@@ -218,7 +222,7 @@ __global__ void __launch_bounds__(256) k_at_loss(LossArgs a) {
             sk[k][tid] = e;
             sum += e;
         }
-        const float v = a.val[i], R = a.ret[i], adv = R - v;
+        const float v = a.val[i], R = a.ret[i], adv = ADV ? advcol[i] : R - v;
         float ent = 0.f, lpa = 0.f, dot = 0.f;
         for (int k = 0; k < A; ++k) {
             const float sx = sk[k][tid] / sum;
@@ -374,6 +378,7 @@ struct ACTrain {
     int* sup = nullptr;                  // the supported view inputs, ascending
     int supK = 0;
     int chunk = kATDefaultChunk;
+    const float* adv = nullptr;          // the advantage column of the next grads / step calls (null: ret - v)
     DevBuf<float> act, part, sp;         // the chunk's activations and intermediates; the K slices' blobs; stats partials
     DevBuf<double> bias;                 // dsum [kATBias], then dpart [slices][kATBias]
     size_t part_slices = 0;
@@ -471,7 +476,8 @@ int at_gradient(ACTrain* h, const mfx_actrain_rows* rows, long long n, float* d_
         const int lb = (m + 255) / 256;
         LossArgs la{Z, VAL, rows->act + r0, rows->ret + r0, DV, h->sp.p + block0 * 4, h->err, m, A, n_rows,
                     (float)h->value_coef, (float)h->ent_coef};
-        k_at_loss<<<lb, 256, 0, st>>>(la);
+        if (h->adv) k_at_loss<true><<<lb, 256, 0, st>>>(la, h->adv + r0);
+        else k_at_loss<false><<<lb, 256, 0, st>>>(la, nullptr);
         block0 += (size_t)lb;
         // ---- row-side backward (NT): C = mask (A W^T [+ C])
         k_at_dd<<<dim3(m, 2), 256, 0, st>>>(D, Z, W(7), DV, mf ? nullptr : W(9), A, DD);
@@ -651,6 +657,13 @@ MFX_API int mfx_actrain_set_chunk_rows(void* handle, int chunk_rows) {
     if (chunk_rows == 0) chunk_rows = kATDefaultChunk;
     if (chunk_rows < 1 || chunk_rows > kATMaxChunk) return fail("actrain_set_chunk_rows: %d (1..%d; 0: the default, %d)", chunk_rows, kATMaxChunk, kATDefaultChunk);
     h->chunk = chunk_rows;
+    return 0;
+}
+
+MFX_API int mfx_actrain_set_advantage(void* handle, const float* d_adv) {
+    auto* h = static_cast<ACTrain*>(handle);
+    if (!h) return fail("actrain: null handle");
+    h->adv = d_adv;
     return 0;
 }
 

@@ -50,7 +50,7 @@ class ACTrainHIP:
         self.use_mf = bool(use_mf)
         L = lib()
         for fn in ("create", "destroy", "set_hyper", "set_state", "get_state", "reset_optimizer", "step_count",
-                   "set_input_support", "set_chunk_rows", "grads", "step", "error"):
+                   "set_input_support", "set_chunk_rows", "set_advantage", "grads", "step", "error"):
             getattr(L, "mfx_actrain_" + fn).restype = ctypes.c_int
         self._L = L
         self.blob_n, self.offsets = acnet_layout(self.V, self.F, self.A, self.use_mf)
@@ -127,7 +127,7 @@ class ACTrainHIP:
     # ------------------------------------------------------------------ the step
     def _rows(self, cols, n):
         """cols: dict of column tensors (obs [.., V], feat [.., F], act i32, ret f32, prob [.., A] with the mean
-        field), CUDA and contiguous, at least n rows each."""
+        field), CUDA and contiguous, at least n rows each; an optional "adv" column is grads' / step's."""
         want = {"obs": (torch.float32, self.V), "feat": (torch.float32, self.F), "act": (torch.int32, 1),
                 "ret": (torch.float32, 1)}
         if self.use_mf:
@@ -144,9 +144,20 @@ class ACTrainHIP:
             setattr(r, k, t.data_ptr())
         return r, n
 
+    def _set_advantage(self, cols, n):
+        """cols.get("adv"): the float32 advantage column of the policy term (n rows; ActorCritic.advantage = "gae"), or
+        None for the default ret - v.  Set on every call, so a handle never keeps a column of an earlier one."""
+        adv = cols.get("adv")
+        if adv is not None:
+            assert adv.is_cuda and adv.is_contiguous() and adv.dtype == torch.float32 and adv.dim() == 1 and \
+                adv.shape[0] >= n, "ACTrainHIP: column adv must be a contiguous float32 CUDA vector of at least n rows"
+        check(self._L.mfx_actrain_set_advantage(self.handle, _P(adv.data_ptr()) if adv is not None else None),
+              "mfx_actrain_set_advantage")
+
     def grads(self, cols, n):
         """(gradient blob, stats (pg_loss, vf_loss, ent_loss, mean value)) of rows [0, n).  No state changes."""
         rows, n = self._rows(cols, n)
+        self._set_advantage(cols, n)
         g = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
         stats = torch.zeros(4, dtype=torch.float32, device="cuda")
         check(self._L.mfx_actrain_grads(self.handle, ctypes.byref(rows), ctypes.c_longlong(n), _P(g.data_ptr()),
@@ -157,6 +168,7 @@ class ACTrainHIP:
         """One gradient over rows [0, n) and one Adam step; -> the stats on the device.  Nothing synchronises: call
         check_error() before trusting the result."""
         rows, n = self._rows(cols, n)
+        self._set_advantage(cols, n)
         stats = torch.zeros(4, dtype=torch.float32, device="cuda")
         check(self._L.mfx_actrain_step(self.handle, ctypes.byref(rows), ctypes.c_longlong(n), _P(stats.data_ptr()),
                                        _stream()), "mfx_actrain_step")

@@ -10,7 +10,8 @@ algo/ac.py:305-320), then one Adam step on pg + value_coef * vf + ent_coef * neg
 act_rollout / train_rollout are the same two on the device rollout loop: the actions go straight into a
 BattleBatch's action buffer, and training runs on the rows a linked RolloutCollector left in the episode buffer,
 in place -- the returns walk each agent's chain of rows (HIP kernel mfx_chain_returns) instead of regrouping the
-rows per agent, and no np.random is drawn.
+rows per agent, and no np.random is drawn.  advantage = "gae" (opt-in) replaces that walk by GAE(lambda)
+over the values of all rows (mfx_chain_gae) and hands the losses an advantage column.
 """
 import os
 import zlib
@@ -38,6 +39,10 @@ class ActorCritic:
     _train_backend = "torch"
     _mean_field = "group"       # the device rollout loops: "group" (the reference's mean), or "neighbors" 
     _mf_radius = 6              # mean_field "neighbors": the Chebyshev radius (the Battle view's)
+    _advantage = "returns"      # train_rollout: "returns" (the reference's return - value), or "gae" 
+    _gae_lambda = 0.95
+    _adv_norm = False
+    ADVANTAGES = ("returns", "gae")
 
     def __init__(self, sess, name, handle, env, value_coef=0.1, ent_coef=0.08, gamma=0.95, batch_size=64,
                  learning_rate=1e-4):
@@ -61,6 +66,8 @@ class ActorCritic:
         self._trainer = None        # ACTrainHIP (train_backend "hip"), made at the first training call
         self._trainer_key = None    # weights_key(self.net) the trainer's parameters were packed from / exported to
         self._draws = 0             # act() calls: the step counter of the device draw
+        self._gae_value = None      # advantage "gae": the values and the advantages of a round's rows (float32, grown
+        self._gae_adv = None        # geometrically, reused across rounds)
         # the draw's seed: the run's torch seed mixed with the model name, so runs seeded alike draw alike and
         # differently seeded runs differ, as tf.multinomial under TF's seed would; np.random is left
         # alone -- the reference consumes it in the replay buffers, and seeded runs must draw the same indices
@@ -91,6 +98,58 @@ class ActorCritic:
     @mf_radius.setter
     def mf_radius(self, value):
         self._mf_radius = mf.check_mf_radius(value)
+
+    @property
+    def advantage(self):
+        """The advantage of the policy term in train_rollout (the device rollout loop): "returns" (the default and the
+        reference's: the discounted return bootstrapped from the chain's last row, minus the value) or "gae" (opt-in,
+        DESIGN 7q: GAE(gae_lambda) along each agent's chain from the f32 values of all rows, replay.chain_gae; the value
+        term regresses on advantage + value).  train(), the host-loop path, refuses a "gae" model."""
+        return self._advantage
+
+    @advantage.setter
+    def advantage(self, value):
+        if value not in self.ADVANTAGES:
+            raise ValueError("advantage %r (one of %s)" % (value, ", ".join(self.ADVANTAGES)))
+        if value != "gae" and self._adv_norm:
+            raise ValueError("advantage %r: adv_norm is set, and normalises the column of advantage \"gae\" -- clear "
+                             "it first" % (value,))
+        self._advantage = value
+
+    @property
+    def gae_lambda(self):
+        """The lambda of advantage = "gae": a number in [0, 1] (default 0.95; 1: the reference's return - value, 0: the
+        one-step TD error)."""
+        return self._gae_lambda
+
+    @gae_lambda.setter
+    def gae_lambda(self, value):
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or \
+                not 0.0 <= float(value) <= 1.0:
+            raise ValueError("gae_lambda must be a number in [0, 1], got %r" % (value,))
+        self._gae_lambda = float(value)
+
+    @property
+    def adv_norm(self):
+        """advantage = "gae" only: normalise the round's advantages to zero mean and unit (population) standard
+        deviation before the losses (replay.adv_normalize).  Default off."""
+        return self._adv_norm
+
+    @adv_norm.setter
+    def adv_norm(self, value):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError("adv_norm must be a bool, got %r" % (value,))
+        if value and self._advantage != "gae":
+            raise ValueError("adv_norm normalises the advantage column of advantage = \"gae\": set that first")
+        self._adv_norm = bool(value)
+
+    def _gae_columns(self, cap):
+        """The model's value and advantage tensors, `cap` rows each -- the capacity of the buffer's row storage, so
+        they grow geometrically with it and serve every later round that fits."""
+        if self._gae_value is None or self._gae_value.numel() < cap:
+            self._gae_value = torch.empty(cap, dtype=torch.float32, device="cuda")
+            self._gae_adv = torch.empty(cap, dtype=torch.float32, device="cuda")
+        return self._gae_value, self._gae_adv
 
     @property
     def train_backend(self):
@@ -174,13 +233,14 @@ class ActorCritic:
     def act(self, **kwargs):
         return self.act_dev(**kwargs).cpu().numpy().astype(np.int32)
 
-    def losses(self, view, feature, action, reward, prob=None, total_rows=None):
+    def losses(self, view, feature, action, reward, prob=None, total_rows=None, adv=None):
         """total_rows: these rows are one chunk of that many (train_rollout) -- every mean becomes the chunk's sum
-        over total_rows, so that the chunks' losses add up to the means over all rows."""
+        over total_rows, so that the chunks' losses add up to the means over all rows.  adv: the rows' advantages
+        (advantage = "gae") in place of (reward - value).detach(); the value term regresses on reward either way."""
         mean = torch.mean if total_rows is None else (lambda x: torch.sum(x) / total_rows)
         policy, value = self.net(view, feature, prob)
         action_mask = torch.nn.functional.one_hot(action.long(), self.num_actions).float()
-        advantage = (reward - value).detach()
+        advantage = (reward - value).detach() if adv is None else adv
         log_policy = torch.log(policy + 1e-6)
         log_prob = torch.sum(log_policy * action_mask, dim=1)
         pg_loss = -mean(advantage * log_prob)
@@ -189,6 +249,9 @@ class ActorCritic:
         return pg_loss, vf_loss, neg_entropy, value
 
     def train(self):
+        if self._advantage != "returns":
+            raise ValueError("train: advantage %r runs on the device rollout loop (train_rollout / "
+                             "play_rollout_episodes); the host loops train on the reference's returns" % self._advantage)
         got = self.replay_buffer.batch()
         self.replay_buffer = tools.EpisodesBuffer(use_mean=self._use_mf)
         if got is None:
@@ -267,6 +330,9 @@ class ActorCritic:
         rows in contiguous chunks of at most chunk_rows -- each chunk's sums divided by the total row count, so the
         chunks' gradients add up to the gradient of the means over all rows -- and one Adam step.  The losses are
         means over rows, so the step-major order changes their float summation order and nothing else.
+        advantage = "gae": the f32 value forward runs over all n rows instead of the tail rows, replay.chain_gae
+        walks the same chains (the reward column becomes advantage + value, the model's adv tensor the advantages,
+        normalised when adv_norm is set), and the policy term of either backend reads that column.
         step=False: no Adam step; returns the gradients (one tensor per parameter, None where there is none).
         Afterwards the rows are cleared; the buffer and its storage are kept."""
         from .. import replay
@@ -282,19 +348,37 @@ class ActorCritic:
         assert chunk >= 1
         c = rows.cols
         prob = c["prob"] if self._use_mf else None
+        gae = self._advantage == "gae"
+        adv = None
+        if gae:
+            if not self._hip_ok():
+                raise ValueError("train_rollout: advantage \"gae\" takes its values from the HIP forward (2..32 actions, "
+                                 "views of at most 4096 floats, at most 256 features)")
+            value, adv = self._gae_columns(rows.cap)
+            value.record_stream(col.eng.torch_stream())
+            adv.record_stream(col.eng.torch_stream())
         with torch.cuda.stream(col.eng.torch_stream()), torch.no_grad():
             tails = c["tail"][:n].nonzero().reshape(-1)
-            p_t = prob[tails] if prob is not None else None
-            if self._hip_ok():
-                _, keep, _ = self._hip_net().forward(c["obs"][tails], c["feat"][tails], p_t, want_policy=False,
-                                                     want_value=True, want_act=False)
+            if gae:
+                # the f32 value of every row (whatever act_precision is), then the walk along the same chains
+                _, v_rows, _ = self._hip_net().forward(c["obs"][:n], c["feat"][:n], prob[:n] if prob is not None else None,
+                                                       want_policy=False, want_value=True, want_act=False)
+                value[:n].copy_(v_rows.reshape(-1))
+                replay.chain_gae(c["rew"][:n], adv, c["prev"], tails, value, self.gamma, self._gae_lambda)
+                if self._adv_norm:
+                    replay.adv_normalize(adv[:n])
             else:
-                _, keep = self.net(c["obs"][tails], c["feat"][tails], p_t)
-            replay.chain_returns(c["rew"][:n], c["prev"], tails, keep.float().reshape(-1), self.gamma)
+                p_t = prob[tails] if prob is not None else None
+                if self._hip_ok():
+                    _, keep, _ = self._hip_net().forward(c["obs"][tails], c["feat"][tails], p_t, want_policy=False,
+                                                         want_value=True, want_act=False)
+                else:
+                    _, keep = self.net(c["obs"][tails], c["feat"][tails], p_t)
+                replay.chain_returns(c["rew"][:n], c["prev"], tails, keep.float().reshape(-1), self.gamma)
         torch.cuda.current_stream().wait_stream(col.eng.torch_stream())
         if self._train_backend == "hip":
             # the rows come from the engine: the view layer runs over its support, as act_rollout's does
-            cols = {"obs": c["obs"], "feat": c["feat"], "act": c["act"], "ret": c["rew"], "prob": prob}
+            cols = {"obs": c["obs"], "feat": c["feat"], "act": c["act"], "ret": c["rew"], "prob": prob, "adv": adv}
             grads, stats = self._hip_train(cols, n, step=step, support=col.eng.view_support(col.group),
                                            chunk_rows=chunk_rows)
             col.eng.torch_stream().wait_stream(torch.cuda.current_stream())
@@ -308,7 +392,8 @@ class ActorCritic:
         for a in range(0, n, chunk):
             b = min(a + chunk, n)
             pg, vf, ent, value = self.losses(c["obs"][a:b], c["feat"][a:b], c["act"][a:b], c["rew"][a:b],
-                                             prob[a:b] if prob is not None else None, total_rows=n)
+                                             prob[a:b] if prob is not None else None, total_rows=n,
+                                             adv=adv[a:b] if adv is not None else None)
             (pg + vf + ent).backward()
             sums += torch.stack([pg.detach(), vf.detach(), ent.detach(), value.detach().sum() / n]).double()
         col.eng.torch_stream().wait_stream(torch.cuda.current_stream())     # the next round writes these rows

@@ -285,6 +285,43 @@ def chain_returns(rew, prev, tails, values, gamma=0.95, numpy1=True):
     return rew
 
 
+def chain_gae(rew, adv, prev, tails, values, gamma=0.95, lam=0.95):
+    """GAE(lambda) along the chains chain_returns walks (HIP kernel k_chain_gae; the contract is mfx_chain_gae's in
+    include/magent_amd.h): `values` holds one float32 value per row of `rew`; the advantages go to the float32 column
+    `adv` and `rew` becomes advantage + value, in place.  -> (rew, adv).  gamma and lam must lie in [0, 1]
+    (ValueError); a row index outside its chain's rows raises IndexError (the walk stops before it; the call
+    synchronises the current stream to know)."""
+    if not (0.0 <= gamma <= 1.0 and 0.0 <= lam <= 1.0):
+        raise ValueError("chain_gae: gamma %r and lambda %r must lie in [0, 1]" % (gamma, lam))
+    assert rew.is_cuda and rew.dtype == torch.float32 and rew.is_contiguous()
+    n = len(rew)
+    assert adv.is_cuda and adv.dtype == torch.float32 and adv.is_contiguous() and len(adv) >= n
+    assert values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and len(values) >= n
+    assert prev.dtype == torch.int64 and prev.is_contiguous() and len(prev) >= n
+    tails = tails.to(torch.int64).contiguous()
+    L = lib()
+    L.mfx_chain_gae.restype = ctypes.c_int
+    if L.mfx_chain_gae(ctypes.c_void_p(rew.data_ptr()), ctypes.c_void_p(adv.data_ptr()),
+                       ctypes.c_void_p(prev.data_ptr()), ctypes.c_void_p(tails.data_ptr()),
+                       ctypes.c_void_p(values.data_ptr()), ctypes.c_int64(len(tails)), ctypes.c_int64(n),
+                       ctypes.c_double(gamma), ctypes.c_double(lam),
+                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
+        L.mfx_last_error.restype = ctypes.c_char_p
+        raise IndexError(L.mfx_last_error().decode())
+    return rew, adv
+
+
+def adv_normalize(adv):
+    """adv <- (adv - mean) / (std + 1e-8) in place on the float32 column `adv` (mfx_adv_normalize: mean and population
+    standard deviation in float64, one summation order per length, no atomics); nothing is read back."""
+    assert adv.is_cuda and adv.dtype == torch.float32 and adv.is_contiguous()
+    L = lib()
+    L.mfx_adv_normalize.restype = ctypes.c_int
+    check(L.mfx_adv_normalize(ctypes.c_void_p(adv.data_ptr()), ctypes.c_int64(adv.numel()),
+                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "mfx_adv_normalize")
+    return adv
+
+
 def chain_links(keys):
     """Host restatement of the linked collector's two columns, for the tests: for the key column of step-major
     rows, prev[r] = the latest earlier row with the same key (or -1) and tail[r] = no later row has it."""

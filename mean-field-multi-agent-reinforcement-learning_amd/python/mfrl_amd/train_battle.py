@@ -10,6 +10,7 @@
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann ...   # sample from softmax(q / eps)
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann --target boltzmann ...   # + the paper's v^MF target
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --mean_field neighbors --mf_radius 6 ...   # the paper's neighbourhood mean action
+    python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes --advantage gae --gae_lambda 0.95 --adv_norm ...   # GAE(lambda) advantages, normalised per round
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --eval_every 10 --eval_oppo rush ...   # + a round against the scripted opponent, logged to data/eval_<algo>.jsonl
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
@@ -84,6 +85,14 @@ def main(argv=None):
                              "the agents of its group within --mf_radius cells of it)")
     parser.add_argument("--mf_radius", type=int, default=None,
                         help="with --mean_field neighbors: the Chebyshev radius, >= 0 (default 6, the view's)")
+    parser.add_argument("--advantage", type=str, choices=["returns", "gae"], default="returns",
+                        help="ac / mfac with --rollout_episodes: the advantage of the policy term -- returns (the "
+                             "reference: the bootstrapped discounted return minus the value) or gae (GAE(lambda) along "
+                             "each agent's episode chain, from the values of all rows)")
+    parser.add_argument("--gae_lambda", type=float, default=None,
+                        help="with --advantage gae: lambda in [0, 1] (default 0.95)")
+    parser.add_argument("--adv_norm", action="store_true",
+                        help="with --advantage gae: normalise a round's advantages to zero mean and unit deviation")
     parser.add_argument("--eval_every", type=int, default=0,
                         help="after every K-th round play one evaluation round of the main model against a scripted "
                              "opponent on the device rollout loop and log the outcome (0: off)")
@@ -119,6 +128,19 @@ def main(argv=None):
             parser.error("--mf_radius is the radius of --mean_field neighbors: give that too")
         if args.mf_radius < 0:
             parser.error("--mf_radius must be >= 0")
+    if args.advantage != "returns":
+        if args.algo not in ("ac", "mfac"):
+            parser.error("--advantage gae is the advantage of an actor-critic model: --algo ac or mfac (mfq / il train on "
+                         "their Q targets)")
+        if not args.rollout_episodes:
+            parser.error("--advantage gae runs on the device rollout loop: give --rollout_episodes")
+    if args.gae_lambda is not None:
+        if args.advantage != "gae":
+            parser.error("--gae_lambda is the lambda of --advantage gae: give that too")
+        if not 0.0 <= args.gae_lambda <= 1.0:
+            parser.error("--gae_lambda must be in [0, 1]")
+    if args.adv_norm and args.advantage != "gae":
+        parser.error("--adv_norm normalises the advantages of --advantage gae: give that too")
     if args.target != "max" and args.algo not in ("mfq", "il"):
         parser.error("--target boltzmann bootstraps from the Q values: --algo mfq or il (ac / mfac train on their "
                      "returns)")
@@ -181,6 +203,12 @@ def main(argv=None):
             m.mean_field = args.mean_field
             if args.mf_radius is not None:
                 m.mf_radius = args.mf_radius
+        if args.advantage != "returns":
+            m.advantage = args.advantage
+            if args.gae_lambda is not None:
+                m.gae_lambda = args.gae_lambda
+            if args.adv_norm:
+                m.adv_norm = True
     play_handle = play
     if args.envs > 1:
         from .battle import BattleBatch
