@@ -15,15 +15,12 @@ import numpy as np
 import torch
 
 from . import check, lib
+from .abi import ptr, stream, struct
 from .policy import acnet_layout, pack_acnet, unpack_acnet
 
-_P = ctypes.c_void_p
 PARAMS, ADAM_M, ADAM_V = 0, 1, 2
 _ERRORS = {1: "an action outside [0, n_action)"}
-
-
-class _Rows(ctypes.Structure):                # mfx_actrain_rows (include/magent_amd.h)
-    _fields_ = [(k, ctypes.c_void_p) for k in ("obs", "feat", "act", "ret", "prob")]
+_Rows = struct("mfx_actrain_rows")
 
 
 class ACTrainError(IndexError):
@@ -36,10 +33,6 @@ def supported(view_space, feature_space, num_actions):
             2 <= int(num_actions) <= 32)
 
 
-def _stream():
-    return _P(torch.cuda.current_stream().cuda_stream)
-
-
 class ACTrainHIP:
     def __init__(self, view_space, feature_space, num_actions, use_mf=False, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  value_coef=0.1, ent_coef=0.08, chunk_rows=None):
@@ -48,13 +41,9 @@ class ACTrainHIP:
                              "2..32 actions; got %r, %r, %r" % (tuple(view_space), tuple(feature_space), num_actions))
         self.V, self.F, self.A = int(np.prod(view_space)), int(feature_space[0]), int(num_actions)
         self.use_mf = bool(use_mf)
-        L = lib()
-        for fn in ("create", "destroy", "set_hyper", "set_state", "get_state", "reset_optimizer", "step_count",
-                   "set_input_support", "set_chunk_rows", "set_advantage", "grads", "step", "error"):
-            getattr(L, "mfx_actrain_" + fn).restype = ctypes.c_int
-        self._L = L
+        self._L = L = lib()
         self.blob_n, self.offsets = acnet_layout(self.V, self.F, self.A, self.use_mf)
-        hdl = _P()
+        hdl = ctypes.c_void_p()
         check(L.mfx_actrain_create(self.V, self.F, self.A, int(self.use_mf), ctypes.byref(hdl)), "mfx_actrain_create")
         self.handle = hdl
         self._support = None
@@ -68,9 +57,8 @@ class ACTrainHIP:
             self.handle = None
 
     def set_hyper(self, lr, betas=(0.9, 0.999), eps=1e-8, value_coef=0.1, ent_coef=0.08):
-        D = ctypes.c_double
-        check(self._L.mfx_actrain_set_hyper(self.handle, D(lr), D(betas[0]), D(betas[1]), D(eps), D(value_coef),
-                                            D(ent_coef)), "mfx_actrain_set_hyper")
+        check(self._L.mfx_actrain_set_hyper(self.handle, lr, betas[0], betas[1], eps, value_coef, ent_coef),
+              "mfx_actrain_set_hyper")
 
     def set_chunk_rows(self, chunk_rows):
         """Rows per chunk of kept activations (0 / None: the default, 12288)."""
@@ -80,14 +68,14 @@ class ACTrainHIP:
     def set_state(self, which, blob):
         """blob: float32 CUDA tensor of blob_n floats in pack_acnet's layout.  Setting PARAMS keeps the moments."""
         blob = blob.to(device="cuda", dtype=torch.float32).contiguous()
-        check(self._L.mfx_actrain_set_state(self.handle, int(which), _P(blob.data_ptr()), ctypes.c_size_t(blob.numel()),
-                                            _stream()), "mfx_actrain_set_state")
+        check(self._L.mfx_actrain_set_state(self.handle, int(which), ptr(blob), blob.numel(), stream()),
+              "mfx_actrain_set_state")
         blob.record_stream(torch.cuda.current_stream())
 
     def get_state(self, which):
         out = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
-        check(self._L.mfx_actrain_get_state(self.handle, int(which), _P(out.data_ptr()), ctypes.c_size_t(self.blob_n),
-                                            _stream()), "mfx_actrain_get_state")
+        check(self._L.mfx_actrain_get_state(self.handle, int(which), ptr(out), self.blob_n, stream()),
+              "mfx_actrain_get_state")
         return out
 
     def load(self, net):
@@ -101,7 +89,7 @@ class ACTrainHIP:
         return blob
 
     def reset_optimizer(self):
-        check(self._L.mfx_actrain_reset_optimizer(self.handle, _stream()), "mfx_actrain_reset_optimizer")
+        check(self._L.mfx_actrain_reset_optimizer(self.handle, stream()), "mfx_actrain_reset_optimizer")
 
     def step_count(self):
         t = ctypes.c_longlong()
@@ -113,14 +101,14 @@ class ACTrainHIP:
         caller's contract of ACNetHIP.set_input_support).  Waits for the current stream."""
         if mask is None:
             if self._support is not None:
-                check(self._L.mfx_actrain_set_input_support(self.handle, None, 0, _stream()),
+                check(self._L.mfx_actrain_set_input_support(self.handle, None, 0, stream()),
                       "mfx_actrain_set_input_support")
             self._support = None
             return self
         m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8).reshape(-1))
         if self._support is None or not np.array_equal(self._support, m):
-            check(self._L.mfx_actrain_set_input_support(self.handle, m.ctypes.data_as(ctypes.c_void_p), int(m.size),
-                                                        _stream()), "mfx_actrain_set_input_support")
+            check(self._L.mfx_actrain_set_input_support(self.handle, ptr(m), int(m.size), stream()),
+                  "mfx_actrain_set_input_support")
             self._support = m.copy()
         return self
 
@@ -151,8 +139,7 @@ class ACTrainHIP:
         if adv is not None:
             assert adv.is_cuda and adv.is_contiguous() and adv.dtype == torch.float32 and adv.dim() == 1 and \
                 adv.shape[0] >= n, "ACTrainHIP: column adv must be a contiguous float32 CUDA vector of at least n rows"
-        check(self._L.mfx_actrain_set_advantage(self.handle, _P(adv.data_ptr()) if adv is not None else None),
-              "mfx_actrain_set_advantage")
+        check(self._L.mfx_actrain_set_advantage(self.handle, ptr(adv)), "mfx_actrain_set_advantage")
 
     def grads(self, cols, n):
         """(gradient blob, stats (pg_loss, vf_loss, ent_loss, mean value)) of rows [0, n).  No state changes."""
@@ -160,8 +147,8 @@ class ACTrainHIP:
         self._set_advantage(cols, n)
         g = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
         stats = torch.zeros(4, dtype=torch.float32, device="cuda")
-        check(self._L.mfx_actrain_grads(self.handle, ctypes.byref(rows), ctypes.c_longlong(n), _P(g.data_ptr()),
-                                        _P(stats.data_ptr()), _stream()), "mfx_actrain_grads")
+        check(self._L.mfx_actrain_grads(self.handle, ctypes.byref(rows), n, ptr(g), ptr(stats), stream()),
+              "mfx_actrain_grads")
         return g, stats
 
     def step(self, cols, n):
@@ -170,14 +157,13 @@ class ACTrainHIP:
         rows, n = self._rows(cols, n)
         self._set_advantage(cols, n)
         stats = torch.zeros(4, dtype=torch.float32, device="cuda")
-        check(self._L.mfx_actrain_step(self.handle, ctypes.byref(rows), ctypes.c_longlong(n), _P(stats.data_ptr()),
-                                       _stream()), "mfx_actrain_step")
+        check(self._L.mfx_actrain_step(self.handle, ctypes.byref(rows), n, ptr(stats), stream()), "mfx_actrain_step")
         return stats
 
     def error(self):
         """Synchronise; (code, bad value) of the sticky device error, cleared (0: none)."""
         code, bad = ctypes.c_int(), ctypes.c_longlong()
-        check(self._L.mfx_actrain_error(self.handle, ctypes.byref(code), ctypes.byref(bad), _stream()),
+        check(self._L.mfx_actrain_error(self.handle, ctypes.byref(code), ctypes.byref(bad), stream()),
               "mfx_actrain_error")
         return code.value, bad.value
 

@@ -18,28 +18,21 @@ import magent
 from magent.gridworld import GridWorld
 
 from . import check, lib
+from .abi import bind, ptr
 
 GET_NUM, GET_REWARD, GET_ID, GET_ALIVE, GET_POS, GET_HP = range(6)
+
+
+def _nbytes(a):
+    """Bytes of a torch tensor or a numpy array."""
+    return a.numel() * a.element_size() if hasattr(a, "numel") else a.nbytes
 
 
 class BattleBatch:
     def __init__(self, map_size, n_envs, config="battle", stream=None):
         L = magent.load_library(lib()._name)
         self.env = GridWorld(config, map_size=map_size, lib=L) if isinstance(config, str) else GridWorld(config, lib=L)
-        self._dll = L.dll
-        for fn in ("mfx_battle_set_num_envs", "mfx_battle_set_stream", "mfx_battle_observe",
-                   "mfx_battle_set_action", "mfx_battle_step", "mfx_battle_get", "mfx_battle_clear_dead",
-                   "mfx_battle_sync", "mfx_battle_rollout_init", "mfx_battle_rollout_step",
-                   "mfx_battle_rollout_buffer", "mfx_battle_rollout_copy", "mfx_battle_rollout_rowcap",
-                   "mfx_battle_rollout_info", "mfx_battle_group_capacity", "mfx_battle_rollout_set_substeps",
-                   "mfx_battle_rollout_copy_at", "mfx_battle_rollout_check", "mfx_battle_rollout_path",
-                   "mfx_battle_rollout_policy_step", "mfx_battle_rollout_sum_lanes", "mfx_battle_rollout_mean_stride",
-                   "mfx_battle_rollout_get_substeps", "mfx_battle_rollout_policy_path", "mfx_battle_rollout_write"):
-            try:
-                getattr(self._dll, fn).restype = ctypes.c_int
-            except AttributeError:          # an older build of the library (A/B runs)
-                pass
-        self._dll.mfx_last_error.restype = ctypes.c_char_p
+        self._dll = bind(L.dll)             # (a CDLL of its own: the engine's entry points are declared on it too)
         self.handles = self.env.get_handles()
         self.n_envs = n_envs
         self.game = self.env.game
@@ -47,14 +40,12 @@ class BattleBatch:
         if stream is not None:
             self.set_stream(stream)
 
-    def _check(self, ret, what):
-        if ret != 0:
-            raise magent.EngineError("%s failed: %s" % (what, self._dll.mfx_last_error().decode()))
+    _check = staticmethod(check)
 
     def set_stream(self, stream):
         """stream: a torch.cuda.Stream (or a raw hipStream_t as int)."""
         raw = getattr(stream, "cuda_stream", stream)
-        self._check(self._dll.mfx_battle_set_stream(self.game, ctypes.c_void_p(raw)), "set_stream")
+        self._check(self._dll.mfx_battle_set_stream(self.game, raw), "set_stream")
         self._stream_raw = raw
 
     def stream_handle(self):
@@ -82,19 +73,16 @@ class BattleBatch:
         return c.value
 
     def observe(self, group, view, feature, rowcap):
-        self._check(self._dll.mfx_battle_observe(self.game, group, ctypes.c_void_p(view.data_ptr()),
-                                                 ctypes.c_void_p(feature.data_ptr()), rowcap), "observe")
+        self._check(self._dll.mfx_battle_observe(self.game, group, ptr(view), ptr(feature), rowcap), "observe")
 
     def set_action(self, group, actions, rowcap):
-        self._check(self._dll.mfx_battle_set_action(self.game, group, ctypes.c_void_p(actions.data_ptr()), rowcap),
-                    "set_action")
+        self._check(self._dll.mfx_battle_set_action(self.game, group, ptr(actions), rowcap), "set_action")
 
     def step(self, done=None):
-        ptr = ctypes.c_void_p(done.data_ptr()) if done is not None else ctypes.c_void_p()
-        self._check(self._dll.mfx_battle_step(self.game, ptr), "step")
+        self._check(self._dll.mfx_battle_step(self.game, ptr(done)), "step")
 
     def get(self, group, what, out, rowcap):
-        self._check(self._dll.mfx_battle_get(self.game, group, what, ctypes.c_void_p(out.data_ptr()), rowcap), "get")
+        self._check(self._dll.mfx_battle_get(self.game, group, what, ptr(out), rowcap), "get")
 
     def clear_dead(self):
         self._check(self._dll.mfx_battle_clear_dead(self.game), "clear_dead")
@@ -117,8 +105,7 @@ class BattleBatch:
         P = ctypes.POINTER(ctypes.c_int)
         px = (P * G)(*[a.ctypes.data_as(P) for a in xs])
         py = (P * G)(*[a.ctypes.data_as(P) for a in ys])
-        self._check(self._dll.mfx_battle_rollout_init(self.game, n, px, py, max_steps, ctypes.c_float(eps),
-                                                      ctypes.c_uint(seed), int(stagger)),
+        self._check(self._dll.mfx_battle_rollout_init(self.game, n, px, py, max_steps, eps, seed, int(stagger)),
                     "rollout_init")
         rc = ctypes.c_int()
         self._dll.mfx_battle_rollout_rowcap(self.game, ctypes.byref(rc))
@@ -206,14 +193,12 @@ class BattleBatch:
         """GB/s of a write-only float4 stream of total_bytes over this batch's view buffer of `group` (wrapping;
         mfx_store_ceiling, shape index into STORE_SHAPES) on the engine's stream.  Overwrites the views: call it
         only after their last use."""
-        ptr, n = ctypes.c_void_p(), ctypes.c_size_t()
-        self._check(self._dll.mfx_battle_rollout_buffer(self.game, b"view", group, ctypes.byref(ptr), ctypes.byref(n)),
+        buf, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._dll.mfx_battle_rollout_buffer(self.game, b"view", group, ctypes.byref(buf), ctypes.byref(n)),
                     "rollout_buffer")
         ms = ctypes.c_float()
-        self._dll.mfx_store_ceiling.restype = ctypes.c_int
-        self._check(self._dll.mfx_store_ceiling(ptr, n, ctypes.c_size_t(int(total_bytes)), int(shape),
-                                                ctypes.c_void_p(self.stream_handle()), ctypes.byref(ms)),
-                    "store_ceiling")
+        self._check(self._dll.mfx_store_ceiling(buf, n, int(total_bytes), int(shape), self.stream_handle(),
+                                                ctypes.byref(ms)), "store_ceiling")
         return (int(total_bytes) // 4096 * 4096) / (ms.value * 1e-3) / 1e9
 
     def view_support(self, group):
@@ -221,18 +206,21 @@ class BattleBatch:
         non-zero, 0 where it is always zero (cells outside the view range carry only the minimap channels)."""
         n = int(np.prod(self.env.get_view_space(self.handles[group])))
         mask = np.zeros(n, dtype=np.uint8)
-        self._dll.mfx_battle_view_support.restype = ctypes.c_int
-        self._check(self._dll.mfx_battle_view_support(self.game, int(group), mask.ctypes.data_as(ctypes.c_void_p), n),
-                    "view_support")
+        self._check(self._dll.mfx_battle_view_support(self.game, int(group), ptr(mask), n), "view_support")
         return mask
+
+    def rollout_buffer(self, name, group=0):
+        """The device address of rollout buffer `name` (`group`: which group's "view" / "feature").  The buffers may
+        move at a rollout_init: take the address again after one."""
+        p, nb = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._dll.mfx_battle_rollout_buffer(self.game, name.encode(), group, ctypes.byref(p),
+                                                        ctypes.byref(nb)), "rollout_buffer")
+        return p.value
 
     def rollout_copy(self, name, dst, group=0, nbytes=None):
         """Copy a device rollout buffer into dst (numpy array or torch tensor, host or device)."""
-        ptr = dst.data_ptr() if hasattr(dst, "data_ptr") else dst.ctypes.data
-        size = nbytes if nbytes is not None else (dst.numel() * dst.element_size() if hasattr(dst, "numel")
-                                                  else dst.nbytes)
-        self._check(self._dll.mfx_battle_rollout_copy(self.game, name.encode(), group, ctypes.c_void_p(ptr),
-                                                      ctypes.c_size_t(size)), "rollout_copy")
+        size = nbytes if nbytes is not None else _nbytes(dst)
+        self._check(self._dll.mfx_battle_rollout_copy(self.game, name.encode(), group, ptr(dst), size), "rollout_copy")
 
     WRITABLE = ("actions",)
 
@@ -242,16 +230,11 @@ class BattleBatch:
         rollout_policy_step acts with) is writable."""
         if name not in self.WRITABLE:
             raise ValueError("rollout_write: buffer %r is not writable (only %s)" % (name, ", ".join(self.WRITABLE)))
-        ptr = src.data_ptr() if hasattr(src, "data_ptr") else src.ctypes.data
-        size = src.numel() * src.element_size() if hasattr(src, "numel") else src.nbytes
-        self._check(self._dll.mfx_battle_rollout_write(self.game, name.encode(), group, ctypes.c_void_p(ptr),
-                                                       ctypes.c_size_t(size)), "rollout_write")
+        self._check(self._dll.mfx_battle_rollout_write(self.game, name.encode(), group, ptr(src), _nbytes(src)),
+                    "rollout_write")
 
     def rollout_copy_at(self, name, dst, offset, group=0, nbytes=None):
         """Copy bytes [offset, offset + nbytes) of a device rollout buffer into dst."""
-        ptr = dst.data_ptr() if hasattr(dst, "data_ptr") else dst.ctypes.data
-        size = nbytes if nbytes is not None else (dst.numel() * dst.element_size() if hasattr(dst, "numel")
-                                                  else dst.nbytes)
-        self._check(self._dll.mfx_battle_rollout_copy_at(self.game, name.encode(), group, ctypes.c_size_t(offset),
-                                                         ctypes.c_void_p(ptr), ctypes.c_size_t(size)),
+        size = nbytes if nbytes is not None else _nbytes(dst)
+        self._check(self._dll.mfx_battle_rollout_copy_at(self.game, name.encode(), group, offset, ptr(dst), size),
                     "rollout_copy_at")

@@ -10,20 +10,12 @@
     q_sample(q, temperature, seed, step)     the Boltzmann draw over Q rows (csrc/qsample.h): the opt-in exploration
                                              of the Q models; no counterpart in the reference, whose act is greedy
 """
-import ctypes
 import math
 
 import torch
 
 from . import check, lib
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .abi import ptr, stream
 
 
 def _dtype(what, **tensors):
@@ -43,10 +35,8 @@ def mean_action(actions, counts, n_action):
     if counts.shape != (B,):
         raise ValueError("mean_action: counts of shape %s for %d rows" % (tuple(counts.shape), B))
     out = torch.empty((B, n_action), dtype=torch.float64, device=actions.device)
-    L = lib()
-    L.mfx_mean_action.restype = ctypes.c_int
-    check(L.mfx_mean_action(_p(actions.contiguous()), _p(counts.contiguous()), B, rowcap, n_action, _p(out),
-                            _stream()), "mfx_mean_action")
+    check(lib().mfx_mean_action(ptr(actions.contiguous()), ptr(counts.contiguous()), B, rowcap, n_action, ptr(out),
+                                stream()), "mfx_mean_action")
     return out
 
 
@@ -91,10 +81,8 @@ def neighbor_mean(pos, actions, counts, n_action, radius, map_w, map_h, out=None
         _dtype("neighbor_mean", out=(out, torch.float32))
         if out.shape != (B, rowcap, n_action) or not out.is_contiguous():
             raise ValueError("neighbor_mean: out of shape %s for [%d, %d, %d]" % (tuple(out.shape), B, rowcap, n_action))
-    L = lib()
-    L.mfx_neighbor_mean.restype = ctypes.c_int
-    check(L.mfx_neighbor_mean(_p(pos.contiguous()), _p(actions.contiguous()), _p(counts.contiguous()), B, rowcap,
-                              int(n_action), int(radius), int(map_w), int(map_h), _p(out), _stream()),
+    check(lib().mfx_neighbor_mean(ptr(pos.contiguous()), ptr(actions.contiguous()), ptr(counts.contiguous()), B, rowcap,
+                                  int(n_action), int(radius), int(map_w), int(map_h), ptr(out), stream()),
           "mfx_neighbor_mean")
     return out
 
@@ -115,9 +103,6 @@ class NeighborMean:
     def __init__(self, eng, group, radius):
         self.eng, self.group, self.radius = eng, int(group), check_mf_radius(radius)
         self.n_action = int(eng.env.get_action_space(eng.handles[self.group])[0])
-        L = eng._dll
-        L.mfx_neighbor_mean_reset.restype = ctypes.c_int
-        L.mfx_neighbor_mean_rollout.restype = ctypes.c_int
         with torch.cuda.stream(eng.torch_stream()):
             self.rows = torch.zeros((eng.n_envs, eng.rowcap, self.n_action), dtype=torch.float32, device="cuda")
             self._state = torch.zeros(2 * eng.n_envs, dtype=torch.int32, device="cuda")
@@ -128,12 +113,12 @@ class NeighborMean:
                 and self.rows.shape[:2] == (eng.n_envs, eng.rowcap))
 
     def reset(self):
-        self.eng._check(self.eng._dll.mfx_neighbor_mean_reset(self.eng.game, self.group, _p(self.rows), _p(self._state)),
-                        "neighbor_mean_reset")
+        self.eng._check(self.eng._dll.mfx_neighbor_mean_reset(self.eng.game, self.group, ptr(self.rows),
+                                                              ptr(self._state)), "neighbor_mean_reset")
 
     def update(self):
-        self.eng._check(self.eng._dll.mfx_neighbor_mean_rollout(self.eng.game, self.group, self.radius, _p(self.rows),
-                                                                _p(self._state)), "neighbor_mean_rollout")
+        self.eng._check(self.eng._dll.mfx_neighbor_mean_rollout(self.eng.game, self.group, self.radius, ptr(self.rows),
+                                                                ptr(self._state)), "neighbor_mean_rollout")
 
 
 def mfq_target(e_q, t_q, rewards, dones, gamma=0.95):
@@ -146,10 +131,8 @@ def mfq_target(e_q, t_q, rewards, dones, gamma=0.95):
             tuple(x.shape) for x in (e_q, t_q, rewards, dones)))
     out = torch.empty(M, dtype=torch.float64, device=e_q.device)
     d = dones.to(torch.uint8).contiguous()
-    L = lib()
-    L.mfx_mfq_target.restype = ctypes.c_int
-    check(L.mfx_mfq_target(_p(e_q.contiguous()), _p(t_q.contiguous()), _p(rewards.contiguous()), _p(d), M, A,
-                           ctypes.c_double(gamma), _p(out), _stream()), "mfx_mfq_target")
+    check(lib().mfx_mfq_target(ptr(e_q.contiguous()), ptr(t_q.contiguous()), ptr(rewards.contiguous()), ptr(d), M, A,
+                               gamma, ptr(out), stream()), "mfx_mfq_target")
     return out
 
 
@@ -178,22 +161,18 @@ def mfq_target_boltzmann(e_q, t_q, rewards, dones, gamma, temperature, want_w=Fa
             tuple(x.shape) for x in (e_q, t_q, rewards, dones)))
     if not 2 <= A <= 32:
         raise ValueError("mfq_target_boltzmann: 2 <= A <= 32, got %d" % A)
-    null = ctypes.c_void_p()
     if isinstance(temperature, torch.Tensor):
         _dtype("mfq_target_boltzmann", temperature=(temperature, torch.float32))
         if temperature.numel() != 1 or not temperature.is_cuda:
             raise ValueError("mfq_target_boltzmann: a tensor temperature is one float32 element on the device")
-        T, d_T = 0.0, _p(temperature)
+        T, d_T = 0.0, ptr(temperature)
     else:
-        T, d_T = check_temperature(temperature, "mfq_target_boltzmann: the temperature"), null
+        T, d_T = check_temperature(temperature, "mfq_target_boltzmann: the temperature"), None
     out = torch.empty(M, dtype=torch.float64, device=e_q.device)
     w = torch.empty((M, A), dtype=torch.float32, device=e_q.device) if want_w else None
     d = dones.to(torch.uint8).contiguous()
-    L = lib()
-    L.mfx_mfq_target_boltzmann.restype = ctypes.c_int
-    check(L.mfx_mfq_target_boltzmann(_p(e_q.contiguous()), _p(t_q.contiguous()), _p(rewards.contiguous()), _p(d), M, A,
-                                     ctypes.c_double(gamma), ctypes.c_float(T), d_T, _p(out), _p(w) if want_w else null,
-                                     _stream()), "mfx_mfq_target_boltzmann")
+    check(lib().mfx_mfq_target_boltzmann(ptr(e_q.contiguous()), ptr(t_q.contiguous()), ptr(rewards.contiguous()), ptr(d),
+                                         M, A, gamma, T, d_T, ptr(out), ptr(w), stream()), "mfx_mfq_target_boltzmann")
     return (out, w) if want_w else out
 
 
@@ -212,12 +191,8 @@ def q_sample(q, temperature, seed, step, group=0, rows=None, want_w=False):
     n, A = q.shape
     act = torch.empty(n, dtype=torch.int32, device=q.device)
     w = torch.empty((n, A), dtype=torch.float32, device=q.device) if want_w else None
-    L = lib()
-    L.mfx_q_sample_rows.restype = ctypes.c_int
-    null = ctypes.c_void_p()
-    check(L.mfx_q_sample_rows(_p(q.contiguous()), _p(rows) if rows is not None else null, n, A, ctypes.c_float(temperature),
-                              ctypes.c_uint32(seed & 0xFFFFFFFF), ctypes.c_uint32(step & 0xFFFFFFFF), int(group),
-                              _p(w) if want_w else null, _p(act), _stream()), "mfx_q_sample")
+    check(lib().mfx_q_sample_rows(ptr(q.contiguous()), ptr(rows), n, A, temperature, seed, step, int(group), ptr(w),
+                                  ptr(act), stream()), "mfx_q_sample")
     return (act, w) if want_w else act
 
 
@@ -232,8 +207,6 @@ def mfac_returns(rewards, offsets, values, gamma=0.95, numpy1=True):
         raise ValueError("mfac_returns: rewards must be contiguous (the returns are written in place)")
     if offsets.dim() != 1 or values.dim() != 1 or len(offsets) != len(values) + 1:
         raise ValueError("mfac_returns: %d offsets for %d values (one more is needed)" % (len(offsets), len(values)))
-    L = lib()
-    L.mfx_mfac_returns.restype = ctypes.c_int
-    check(L.mfx_mfac_returns(_p(rewards), _p(offsets.contiguous()), _p(values.contiguous()), len(values),
-                             ctypes.c_double(gamma), int(bool(numpy1)), _stream()), "mfx_mfac_returns")
+    check(lib().mfx_mfac_returns(ptr(rewards), ptr(offsets.contiguous()), ptr(values.contiguous()), len(values),
+                                 gamma, int(bool(numpy1)), stream()), "mfx_mfac_returns")
     return rewards

@@ -46,26 +46,13 @@ import numpy as np
 import torch
 
 from . import check, lib
-
-_P = ctypes.c_void_p
-
-
-def _ptr(t):
-    return _P(t.data_ptr()) if t is not None else _P()
+from .abi import ptr, stream
 
 
 def rows_scratch(E, rowcap):
     """Ints of the act_rollout row-list scratch: E * rowcap rows, the row count, one total per 64-env chunk
     (include/magent_amd.h, mfx_qnet_act_rollout)."""
     return E * rowcap + 1 + (E + 63) // 64
-
-
-def _stream():
-    return _P(torch.cuda.current_stream().cuda_stream)
-
-
-def _u32(x):
-    return ctypes.c_uint32(x & 0xFFFFFFFF)
 
 
 def _rollout_args(scratch, eng, group, names):
@@ -77,13 +64,8 @@ def _rollout_args(scratch, eng, group, names):
     rows = scratch.get(id(eng))
     if rows is None or rows.numel() < rows_scratch(E, rc):
         rows = scratch[id(eng)] = torch.empty(rows_scratch(E, rc), dtype=torch.int32, device="cuda")
-    ptr = {}
-    for name in names:
-        p, nb = _P(), ctypes.c_size_t()
-        eng._check(eng._dll.mfx_battle_rollout_buffer(eng.game, name.encode(), group if name in ("view", "feature")
-                                                      else 0, ctypes.byref(p), ctypes.byref(nb)), "rollout_buffer")
-        ptr[name] = p
-    return ptr, _P(rows.data_ptr()), _P(rows.data_ptr() + 4 * E * rc)
+    bufs = {name: eng.rollout_buffer(name, group if name in ("view", "feature") else 0) for name in names}
+    return bufs, rows.data_ptr(), rows.data_ptr() + 4 * E * rc
 
 
 PRECISIONS = {"f32": 0, "bf16": 1}      # mfx_qnet_set_precision / mfx_acnet_set_precision
@@ -93,11 +75,9 @@ N_BLOCKS = 18      # w1 b1 w2 b2 wd bd we be wp1 bp1 wp2 bp2 w2d b2d wo bo wq bq
 
 def blob_layout(feature, n_action, use_mf):
     """(floats in the packed blob, the 18 block offsets) -- mfx_qnet_blob_size (host only, no GPU)."""
-    L = lib()
-    L.mfx_qnet_blob_size.restype = ctypes.c_int
     n = ctypes.c_size_t()
     off = (ctypes.c_size_t * N_BLOCKS)()
-    check(L.mfx_qnet_blob_size(int(feature), int(n_action), int(bool(use_mf)), ctypes.byref(n), off),
+    check(lib().mfx_qnet_blob_size(int(feature), int(n_action), int(bool(use_mf)), ctypes.byref(n), off),
           "mfx_qnet_blob_size")
     return n.value, list(off)
 
@@ -187,23 +167,15 @@ class QNetHIP:
         self.precision = precision
         h, w, c = view_space
         self.F, self.A, self.use_mf = int(feature_space[0]), int(num_actions), bool(use_mf)
-        L = lib()
-        for fn in ("mfx_qnet_create", "mfx_qnet_destroy", "mfx_qnet_set_weights", "mfx_qnet_forward",
-                   "mfx_qnet_act_rollout", "mfx_qnet_set_precision", "mfx_qnet_precision"):
-            getattr(L, fn).restype = ctypes.c_int
-        for fn in ("mfx_qnet_forward_sample", "mfx_qnet_act_rollout_sample",     # (absent from older builds, which
-                   "mfx_qnet_act_rollout_rows", "mfx_qnet_act_rollout_rows_sample"):
-            if hasattr(L, fn):                                                   #  the bench scripts may load)
-                getattr(L, fn).restype = ctypes.c_int
-        self._L = L
+        self._L = L = lib()
         self.blob_n, self.offsets = blob_layout(self.F, self.A, self.use_mf)
-        hdl = _P()
+        hdl = ctypes.c_void_p()
         check(L.mfx_qnet_create(int(h), int(w), int(c), self.F, self.A, int(self.use_mf), ctypes.byref(hdl)),
               "mfx_qnet_create")
         self.handle = hdl
         self._rows = {}
         if precision != "f32":
-            check(L.mfx_qnet_set_precision(hdl, PRECISIONS[precision], _P()), "mfx_qnet_set_precision")
+            check(L.mfx_qnet_set_precision(hdl, PRECISIONS[precision], None), "mfx_qnet_set_precision")
 
     def __del__(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
@@ -216,8 +188,7 @@ class QNetHIP:
     def load(self, net):
         """Upload the weights of torch QNet `net` (same shapes)."""
         self._blob = self.pack(net).contiguous()
-        check(self._L.mfx_qnet_set_weights(self.handle, _ptr(self._blob), ctypes.c_size_t(self.blob_n), _stream()),
-              "mfx_qnet_set_weights")
+        check(self._L.mfx_qnet_set_weights(self.handle, ptr(self._blob), self.blob_n, stream()), "mfx_qnet_set_weights")
         return self
 
     # ------------------------------------------------------------------ forward
@@ -241,14 +212,12 @@ class QNetHIP:
         act = torch.empty(n, dtype=torch.int32, device=view.device)
         if temperature is not None:
             w = torch.empty((n, self.A), dtype=torch.float32, device=view.device) if want_w else None
-            check(self._L.mfx_qnet_forward_sample(self.handle, _ptr(view), _ptr(feature),
-                                                  _ptr(prob if self.use_mf else None), int(n), _ptr(q), _ptr(w), _ptr(act),
-                                                  ctypes.c_float(temperature), _u32(seed),
-                                                  _u32(step), _stream()),
-                  "mfx_qnet_forward_sample")
+            check(self._L.mfx_qnet_forward_sample(self.handle, ptr(view), ptr(feature),
+                                                  ptr(prob if self.use_mf else None), int(n), ptr(q), ptr(w), ptr(act),
+                                                  temperature, seed, step, stream()), "mfx_qnet_forward_sample")
             return (q, act, w) if want_w else (q, act)
-        check(self._L.mfx_qnet_forward(self.handle, _ptr(view), _ptr(feature), _ptr(prob if self.use_mf else None),
-                                       int(n), _ptr(q), _ptr(act), _stream()), "mfx_qnet_forward")
+        check(self._L.mfx_qnet_forward(self.handle, ptr(view), ptr(feature), ptr(prob if self.use_mf else None),
+                                       int(n), ptr(q), ptr(act), stream()), "mfx_qnet_forward")
         return q, act
 
     def act(self, view, feature, prob=None, temperature=None, seed=0, step=0):
@@ -269,24 +238,24 @@ class QNetHIP:
         The observation must be current: call eng.rollout_policy_observe() after rollout_init,
         rollout_step or any per-call API use, before the first act_rollout / rollout_policy_step pair."""
         E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
-        ptr, rows, total = _rollout_args(self._rows, eng, group,
+        buf, rows, total = _rollout_args(self._rows, eng, group,
                                          ("view", "feature", "group_num", "mean_action", "actions"))
         if prob_rows is not None:
             if (prob_rows.dtype != torch.float32 or not prob_rows.is_cuda or not prob_rows.is_contiguous()
                     or tuple(prob_rows.shape) != (E, rc, self.A)):
                 raise ValueError("QNetHIP.act_rollout: prob_rows must be a contiguous float32 CUDA tensor [%d, %d, %d], "
                                  "got %s %s" % (E, rc, self.A, prob_rows.dtype, tuple(prob_rows.shape)))
-            prob = (_ptr(prob_rows),)
+            prob = (ptr(prob_rows),)
         else:
-            prob = (ptr["mean_action"], int(eng.mean_stride()))
-        args = (self.handle, ptr["view"], ptr["feature"], ptr["group_num"], *prob, int(E), int(G), int(group), int(rc),
-                rows, total, ptr["actions"])
+            prob = (buf["mean_action"], int(eng.mean_stride()))
+        args = (self.handle, buf["view"], buf["feature"], buf["group_num"], *prob, int(E), int(G), int(group), int(rc),
+                rows, total, buf["actions"])
         if temperature is not None:
-            args += (ctypes.c_float(temperature), _u32(seed), _u32(step))
+            args += (temperature, seed, step)
         fn = {(False, False): "mfx_qnet_act_rollout", (False, True): "mfx_qnet_act_rollout_sample",
               (True, False): "mfx_qnet_act_rollout_rows", (True, True): "mfx_qnet_act_rollout_rows_sample"}[
                   (prob_rows is not None, temperature is not None)]
-        check(getattr(self._L, fn)(*args, _P(eng.stream_handle())), fn)
+        check(getattr(self._L, fn)(*args, eng.stream_handle()), fn)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -297,12 +266,10 @@ AC_BLOCKS = 19     # wv bv we be wd0 wd1 bd wp bp wval bval wep bep wdp bdp wvd 
 
 def acnet_layout(view_floats, feature, n_action, use_mf):
     """(floats in the packed blob, the 19 block offsets) -- mfx_acnet_blob_size (host only, no GPU)."""
-    L = lib()
-    L.mfx_acnet_blob_size.restype = ctypes.c_int
     n = ctypes.c_size_t()
     off = (ctypes.c_size_t * AC_BLOCKS)()
-    check(L.mfx_acnet_blob_size(int(view_floats), int(feature), int(n_action), int(bool(use_mf)), ctypes.byref(n), off),
-          "mfx_acnet_blob_size")
+    check(lib().mfx_acnet_blob_size(int(view_floats), int(feature), int(n_action), int(bool(use_mf)), ctypes.byref(n),
+                                    off), "mfx_acnet_blob_size")
     return n.value, list(off)
 
 
@@ -404,20 +371,15 @@ class ACNetHIP:
         for d in view_space:
             V *= int(d)
         self.V, self.F, self.A, self.use_mf = V, int(feature_space[0]), int(num_actions), bool(use_mf)
-        L = lib()
-        for fn in ("mfx_acnet_create", "mfx_acnet_destroy", "mfx_acnet_set_weights", "mfx_acnet_forward",
-                   "mfx_acnet_act_rollout", "mfx_acnet_set_input_support", "mfx_acnet_input_support_size",
-                   "mfx_acnet_set_precision", "mfx_acnet_precision"):
-            getattr(L, fn).restype = ctypes.c_int
-        self._L = L
+        self._L = L = lib()
         self.blob_n, self.offsets = acnet_layout(self.V, self.F, self.A, self.use_mf)
-        hdl = _P()
+        hdl = ctypes.c_void_p()
         check(L.mfx_acnet_create(self.V, self.F, self.A, int(self.use_mf), ctypes.byref(hdl)), "mfx_acnet_create")
         self.handle = hdl
         self._rows = {}
         self._support = None
         if precision != "f32":
-            check(L.mfx_acnet_set_precision(hdl, PRECISIONS[precision], _P()), "mfx_acnet_set_precision")
+            check(L.mfx_acnet_set_precision(hdl, PRECISIONS[precision], None), "mfx_acnet_set_precision")
 
     def __del__(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
@@ -430,8 +392,7 @@ class ACNetHIP:
     def load(self, net):
         """Upload the weights of torch ACNet `net` (same shapes)."""
         self._blob = self.pack(net).contiguous()
-        check(self._L.mfx_acnet_set_weights(self.handle, _ptr(self._blob), ctypes.c_size_t(self.blob_n), _stream()),
-              "mfx_acnet_set_weights")
+        check(self._L.mfx_acnet_set_weights(self.handle, ptr(self._blob), self.blob_n, stream()), "mfx_acnet_set_weights")
         return self
 
     def set_blob(self, blob):
@@ -439,8 +400,7 @@ class ACNetHIP:
         a device-to-device copy, no packing."""
         assert blob.is_cuda and blob.dtype == torch.float32 and blob.numel() == self.blob_n
         self._blob = blob.contiguous()
-        check(self._L.mfx_acnet_set_weights(self.handle, _ptr(self._blob), ctypes.c_size_t(self.blob_n), _stream()),
-              "mfx_acnet_set_weights")
+        check(self._L.mfx_acnet_set_weights(self.handle, ptr(self._blob), self.blob_n, stream()), "mfx_acnet_set_weights")
         return self
 
     def set_precision(self, precision):
@@ -449,7 +409,7 @@ class ACNetHIP:
         if precision not in PRECISIONS:
             raise ValueError("ACNetHIP: precision %r (one of %s)" % (precision, ", ".join(PRECISIONS)))
         if precision != self.precision:
-            check(self._L.mfx_acnet_set_precision(self.handle, PRECISIONS[precision], _stream()),
+            check(self._L.mfx_acnet_set_precision(self.handle, PRECISIONS[precision], stream()),
                   "mfx_acnet_set_precision")
             self.precision = precision
         return self
@@ -459,12 +419,12 @@ class ACNetHIP:
         dense order.  Later forwards run the view layer over the supported inputs only -- the same results bit for
         bit while the view is zero elsewhere, which the caller guarantees (the engine's observation buffers are)."""
         if mask is None:
-            check(self._L.mfx_acnet_set_input_support(self.handle, None, 0, _stream()), "mfx_acnet_set_input_support")
+            check(self._L.mfx_acnet_set_input_support(self.handle, None, 0, stream()), "mfx_acnet_set_input_support")
             self._support = None
             return self
         m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8).reshape(-1))
-        check(self._L.mfx_acnet_set_input_support(self.handle, m.ctypes.data_as(ctypes.c_void_p), int(m.size),
-                                                  _stream()), "mfx_acnet_set_input_support")
+        check(self._L.mfx_acnet_set_input_support(self.handle, ptr(m), int(m.size), stream()),
+              "mfx_acnet_set_input_support")
         self._support = m.copy()
         return self
 
@@ -492,9 +452,8 @@ class ACNetHIP:
         pol = torch.empty((n, self.A), dtype=torch.float32, device=dev) if want_policy else None
         val = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
         act = torch.empty(n, dtype=torch.int32, device=dev) if want_act else None
-        check(self._L.mfx_acnet_forward(self.handle, _ptr(view), _ptr(feature), _ptr(prob), int(n), _ptr(pol), _ptr(val),
-                                        _ptr(act), _u32(seed), _u32(step),
-                                        _stream()), "mfx_acnet_forward")
+        check(self._L.mfx_acnet_forward(self.handle, ptr(view), ptr(feature), ptr(prob), int(n), ptr(pol), ptr(val),
+                                        ptr(act), seed, step, stream()), "mfx_acnet_forward")
         return pol, val, act
 
     def act(self, view, feature, seed=0, step=0):
@@ -513,10 +472,10 @@ class ACNetHIP:
                 self.set_input_support(m)
         elif self._support is not None:
             self.set_input_support(None)
-        ptr, rows, total = _rollout_args(self._rows, eng, group, ("view", "feature", "group_num", "actions"))
-        check(self._L.mfx_acnet_act_rollout(self.handle, ptr["view"], ptr["feature"], ptr["group_num"], int(E), int(G),
-                                            int(group), int(rc), rows, total, ptr["actions"], _u32(seed), _u32(step),
-                                            _P(eng.stream_handle())), "mfx_acnet_act_rollout")
+        buf, rows, total = _rollout_args(self._rows, eng, group, ("view", "feature", "group_num", "actions"))
+        check(self._L.mfx_acnet_act_rollout(self.handle, buf["view"], buf["feature"], buf["group_num"], int(E), int(G),
+                                            int(group), int(rc), rows, total, buf["actions"], seed, step,
+                                            eng.stream_handle()), "mfx_acnet_act_rollout")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -534,10 +493,7 @@ class RuleHIP:
         h, w, c = (int(x) for x in view_space)
         self.view_space, self.V = (h, w, c), h * w * c
         self.F, self.A = int(feature_space[0]), int(num_actions)
-        L = lib()
-        for fn in ("mfx_rule_create", "mfx_rule_destroy", "mfx_rule_act", "mfx_rule_act_rollout"):
-            getattr(L, fn).restype = ctypes.c_int
-        self._L = L
+        self._L = L = lib()
         v2a = np.ascontiguousarray(np.asarray(view2attack, dtype=np.int32).reshape(-1))
         mv = np.asarray(move_delta, dtype=np.int32).reshape(-1, 2)
         if v2a.size != h * w:
@@ -546,9 +502,8 @@ class RuleHIP:
             raise ValueError("RuleHIP: %d moves, attack_base %d (turn mode is not supported)" % (len(mv), attack_base))
         dx, dy = np.ascontiguousarray(mv[:, 0]), np.ascontiguousarray(mv[:, 1])
         shape = (ctypes.c_int32 * 4)(h, w, c, self.F)
-        as_i32 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))     # noqa: E731
-        hdl = _P()
-        check(L.mfx_rule_create(shape, int(attack_base), self.A, as_i32(v2a), as_i32(dx), as_i32(dy), ctypes.byref(hdl)),
+        hdl = ctypes.c_void_p()
+        check(L.mfx_rule_create(shape, int(attack_base), self.A, ptr(v2a), ptr(dx), ptr(dy), ctypes.byref(hdl)),
               "mfx_rule_create")
         self.handle = hdl
         self._rows = {}
@@ -571,8 +526,8 @@ class RuleHIP:
             raise ValueError("RuleHIP.act: eps must be in [0, 1], got %r" % (eps,))
         act = torch.empty(n, dtype=torch.int32, device=view.device)
         if n:
-            check(self._L.mfx_rule_act(self.handle, _ptr(view), _ptr(feature), int(n), ctypes.c_float(eps), _u32(seed),
-                                       _u32(step), int(group), _ptr(act), _stream()), "mfx_rule_act")
+            check(self._L.mfx_rule_act(self.handle, ptr(view), ptr(feature), int(n), eps, seed, step, int(group),
+                                       ptr(act), stream()), "mfx_rule_act")
         return act
 
     def act_rollout(self, eng, group, eps=0.0, seed=0, step=0):
@@ -581,7 +536,7 @@ class RuleHIP:
         e * rowcap + j)).  Nothing is read back.  Runs on every plan that takes a learned policy; the row-list scratch
         is per engine."""
         E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
-        ptr, rows, total = _rollout_args(self._rows, eng, group, ("view", "feature", "group_num", "actions"))
-        check(self._L.mfx_rule_act_rollout(self.handle, ptr["view"], ptr["feature"], ptr["group_num"], int(E), int(G),
-                                           int(group), int(rc), rows, total, ptr["actions"], ctypes.c_float(eps),
-                                           _u32(seed), _u32(step), _P(eng.stream_handle())), "mfx_rule_act_rollout")
+        buf, rows, total = _rollout_args(self._rows, eng, group, ("view", "feature", "group_num", "actions"))
+        check(self._L.mfx_rule_act_rollout(self.handle, buf["view"], buf["feature"], buf["group_num"], int(E), int(G),
+                                           int(group), int(rc), rows, total, buf["actions"], eps, seed, step,
+                                           eng.stream_handle()), "mfx_rule_act_rollout")

@@ -15,17 +15,14 @@ import ctypes
 import torch
 
 from . import check, lib
+from .abi import ptr, stream, struct
 from .policy import blob_layout, pack_qnet, unpack_qnet
 
-_P = ctypes.c_void_p
 EVAL, TARGET, ADAM_M, ADAM_V = 0, 1, 2, 3
 MAX_BATCH = 4096
 TARGET_RULES = {"max": 0, "boltzmann": 1}      # MFX_QTARGET_MAX / MFX_QTARGET_BOLTZMANN
 _ERRORS = {1: "a sample index outside [0, nb_entries)", 2: "a replay action outside [0, n_action)"}
-
-
-class _Ring(ctypes.Structure):                # mfx_qtrain_ring (include/magent_amd.h)
-    _fields_ = [(k, ctypes.c_void_p) for k in ("obs0", "feat0", "actions", "rewards", "terminals", "masks", "prob")]
+_Ring = struct("mfx_qtrain_ring")
 
 
 class QTrainError(IndexError):
@@ -37,10 +34,6 @@ def supported(view_space, feature_space, num_actions):
     return tuple(view_space) == (13, 13, 7) and 1 <= int(feature_space[0]) <= 256 and 1 <= int(num_actions) <= 32
 
 
-def _stream():
-    return _P(torch.cuda.current_stream().cuda_stream)
-
-
 class QTrainHIP:
     def __init__(self, view_space, feature_space, num_actions, use_mf=False, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  tau=0.005, gamma=0.95):
@@ -48,13 +41,9 @@ class QTrainHIP:
             raise ValueError("QTrainHIP: the HIP training step takes the Battle view (13, 13, 7), feature <= 256 and at "
                              "most 32 actions; got %r, %r, %r" % (tuple(view_space), tuple(feature_space), num_actions))
         self.F, self.A, self.use_mf = int(feature_space[0]), int(num_actions), bool(use_mf)
-        L = lib()
-        for fn in ("create", "destroy", "set_hyper", "set_target", "set_state", "get_state", "reset_optimizer", "step_count", "grads",
-                   "run", "error"):
-            getattr(L, "mfx_qtrain_" + fn).restype = ctypes.c_int
-        self._L = L
+        self._L = L = lib()
         self.blob_n, self.offsets = blob_layout(self.F, self.A, self.use_mf)
-        hdl = _P()
+        hdl = ctypes.c_void_p()
         check(L.mfx_qtrain_create(self.F, self.A, int(self.use_mf), ctypes.byref(hdl)), "mfx_qtrain_create")
         self.handle = hdl
         self.target_rule = "max"
@@ -66,9 +55,7 @@ class QTrainHIP:
             self.handle = None
 
     def set_hyper(self, lr, betas=(0.9, 0.999), eps=1e-8, tau=0.005, gamma=0.95):
-        D = ctypes.c_double
-        check(self._L.mfx_qtrain_set_hyper(self.handle, D(lr), D(betas[0]), D(betas[1]), D(eps), D(tau), D(gamma)),
-              "mfx_qtrain_set_hyper")
+        check(self._L.mfx_qtrain_set_hyper(self.handle, lr, betas[0], betas[1], eps, tau, gamma), "mfx_qtrain_set_hyper")
 
     def set_target(self, rule, temperature=0.1):
         """The rule of the minibatches' target y, for the grads / run calls that follow: "max" (the default: the target
@@ -78,22 +65,21 @@ class QTrainHIP:
         leaves the handle as it was."""
         if rule not in TARGET_RULES:
             raise ValueError("QTrainHIP.set_target: rule %r (one of %s)" % (rule, ", ".join(TARGET_RULES)))
-        check(self._L.mfx_qtrain_set_target(self.handle, TARGET_RULES[rule], ctypes.c_float(temperature)),
-              "mfx_qtrain_set_target")
+        check(self._L.mfx_qtrain_set_target(self.handle, TARGET_RULES[rule], temperature), "mfx_qtrain_set_target")
         self.target_rule = rule
 
     # ------------------------------------------------------------------ state
     def set_state(self, which, blob):
         """blob: float32 CUDA tensor of blob_n floats in pack_qnet's layout.  Setting EVAL or TARGET keeps the moments."""
         blob = blob.to(device="cuda", dtype=torch.float32).contiguous()
-        check(self._L.mfx_qtrain_set_state(self.handle, int(which), _P(blob.data_ptr()), ctypes.c_size_t(blob.numel()),
-                                           _stream()), "mfx_qtrain_set_state")
+        check(self._L.mfx_qtrain_set_state(self.handle, int(which), ptr(blob), blob.numel(), stream()),
+              "mfx_qtrain_set_state")
         blob.record_stream(torch.cuda.current_stream())
 
     def get_state(self, which):
         out = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
-        check(self._L.mfx_qtrain_get_state(self.handle, int(which), _P(out.data_ptr()), ctypes.c_size_t(self.blob_n),
-                                           _stream()), "mfx_qtrain_get_state")
+        check(self._L.mfx_qtrain_get_state(self.handle, int(which), ptr(out), self.blob_n, stream()),
+              "mfx_qtrain_get_state")
         return out
 
     def load(self, eval_net, target_net):
@@ -109,7 +95,7 @@ class QTrainHIP:
         unpack_qnet(self.get_state(TARGET), target_net, self.F, self.A, self.use_mf, layout)
 
     def reset_optimizer(self):
-        check(self._L.mfx_qtrain_reset_optimizer(self.handle, _stream()), "mfx_qtrain_reset_optimizer")
+        check(self._L.mfx_qtrain_reset_optimizer(self.handle, stream()), "mfx_qtrain_reset_optimizer")
 
     def step_count(self):
         t = ctypes.c_longlong()
@@ -151,8 +137,8 @@ class QTrainHIP:
         idx, B = self._idx(idx, n, ring.rows)
         g = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
         stats = torch.zeros(2, dtype=torch.float32, device="cuda")
-        check(self._L.mfx_qtrain_grads(self.handle, ctypes.byref(ring), ctypes.c_longlong(int(n)), _P(idx.data_ptr()), B,
-                                       _P(g.data_ptr()), _P(stats.data_ptr()), _stream()), "mfx_qtrain_grads")
+        check(self._L.mfx_qtrain_grads(self.handle, ctypes.byref(ring), int(n), ptr(idx), B, ptr(g), ptr(stats), stream()),
+              "mfx_qtrain_grads")
         idx.record_stream(torch.cuda.current_stream())
         return g, stats
 
@@ -165,15 +151,15 @@ class QTrainHIP:
         idx, B = self._idx(idx, n, ring.rows)
         nb = int(idx.shape[0])
         stats = torch.zeros((nb, 2), dtype=torch.float32, device="cuda")
-        check(self._L.mfx_qtrain_run(self.handle, ctypes.byref(ring), ctypes.c_longlong(int(n)), _P(idx.data_ptr()), nb, B,
-                                     _P(stats.data_ptr()), _stream()), "mfx_qtrain_run")
+        check(self._L.mfx_qtrain_run(self.handle, ctypes.byref(ring), int(n), ptr(idx), nb, B, ptr(stats), stream()),
+              "mfx_qtrain_run")
         idx.record_stream(torch.cuda.current_stream())
         return stats
 
     def error(self):
         """Synchronise; (code, bad value) of the sticky device error, cleared (0: none)."""
         code, bad = ctypes.c_int(), ctypes.c_longlong()
-        check(self._L.mfx_qtrain_error(self.handle, ctypes.byref(code), ctypes.byref(bad), _stream()), "mfx_qtrain_error")
+        check(self._L.mfx_qtrain_error(self.handle, ctypes.byref(code), ctypes.byref(bad), stream()), "mfx_qtrain_error")
         return code.value, bad.value
 
     def check_error(self):

@@ -28,6 +28,7 @@ import os
 import numpy as np
 
 from . import check, lib
+from .abi import bind, ptr, struct
 
 MAX_ENVS, HEAD, CARRY = 16, 6, 4
 VALID, N, EP_BEFORE, EP_AFTER, STEPS = 0, 1, 3, 4, 5          # the head's words
@@ -53,27 +54,10 @@ class TraceMismatch(RuntimeError):
                               % (env, step, group, field, (" (" + detail + ")") if detail else ""))
 
 
-class _TraceSrc(ctypes.Structure):        # mfx_trace_src (include/magent_amd.h)
-    _fields_ = ([(k, ctypes.c_void_p) for k in ("group_num", "alive", "stats", "agent_steps", "actions", "ids",
-                                                "rewards", "rng")] +
-                [(k, ctypes.c_int32) for k in ("n_envs", "n_groups", "rowcap")])
-
-
-class _TraceDst(ctypes.Structure):        # mfx_trace_dst
-    _fields_ = ([(k, ctypes.c_void_p) for k in ("envs", "carry", "head", "actions", "ids", "rewards", "alive",
-                                                "state", "seeds")] +
-                [("cap_steps", ctypes.c_int64), ("n_watch", ctypes.c_int32)])
-
-
+_TraceSrc, _TraceDst = struct("mfx_trace_src"), struct("mfx_trace_dst")
 DST_NAMES = ("envs", "carry", "head", "actions", "ids", "rewards", "alive", "state", "seeds")
 SRC_NAMES = ("group_num", "alive", "stats", "agent_steps", "actions", "ids", "rewards", "rng")
-
-
-def trace_lib():
-    L = lib()
-    for fn in ("mfx_trace_attach", "mfx_trace_update", "mfx_trace_sizes"):
-        getattr(L, fn).restype = ctypes.c_int
-    return L
+trace_lib = lib                         # (the name the kernel tests reach the library by)
 
 
 def error_text(word):
@@ -122,15 +106,12 @@ class RolloutRecorder:
         self.eng, self.cap_steps = eng, int(cap_steps)
         self.envs = check_watch(envs, eng.n_envs, "RolloutRecorder")
         self._h_envs = (ctypes.c_int32 * len(self.envs))(*self.envs)
-        self._L = trace_lib()
+        self._L = lib()
         self._bufs = self._src = self._dst = self._shape = self._round = self.trace = None
         self._t = 0
 
-    def _buffer(self, name):
-        p, nb = ctypes.c_void_p(), ctypes.c_size_t()
-        self.eng._check(self.eng._dll.mfx_battle_rollout_buffer(self.eng.game, name.encode(), 0, ctypes.byref(p),
-                                                                ctypes.byref(nb)), "rollout_buffer")
-        return p.value
+    def _buffer(self, name):            # (the kernel tests put synthetic device arrays behind this)
+        return self.eng.rollout_buffer(name)
 
     def _structs(self):
         import torch
@@ -138,13 +119,13 @@ class RolloutRecorder:
         E, rc = eng.n_envs, eng.rowcap
         if self._shape != (rc,):
             sizes = (ctypes.c_size_t * 9)()
-            check(self._L.mfx_trace_sizes(K, rc, ctypes.c_int64(self.cap_steps), sizes), "mfx_trace_sizes")
+            check(self._L.mfx_trace_sizes(K, rc, self.cap_steps, sizes), "mfx_trace_sizes")
             with torch.cuda.stream(eng.torch_stream()):
                 self._bufs = [torch.zeros((int(n) + 7) // 8, dtype=torch.int64, device="cuda") for n in sizes]
             self._shape = (rc,)
         # (the rollout buffers may move at a rollout_init: their addresses are taken again at every attach)
         self._src = _TraceSrc(*[self._buffer(k) for k in SRC_NAMES], E, len(eng.handles), rc)
-        self._dst = _TraceDst(*[b.data_ptr() for b in self._bufs], self.cap_steps, K)
+        self._dst = _TraceDst(*[ptr(b) for b in self._bufs], self.cap_steps, K)
 
     def attach(self, map_size, max_steps, placement):
         """After rollout_policy_observe, before the first policy step of the round.  map_size, max_steps and placement
@@ -153,13 +134,13 @@ class RolloutRecorder:
         self._round = (int(map_size), int(max_steps), [np.asarray(p, np.int32) for p in placement])
         self._t = 0
         check(self._L.mfx_trace_attach(ctypes.byref(self._src), ctypes.byref(self._dst), self._h_envs,
-                                       ctypes.c_void_p(self.eng.stream_handle())), "mfx_trace_attach")
+                                       self.eng.stream_handle()), "mfx_trace_attach")
 
     def update(self):
         """After every rollout_policy_step, exactly once."""
         assert self._round is not None, "RolloutRecorder.update() before attach()"
-        check(self._L.mfx_trace_update(ctypes.byref(self._src), ctypes.byref(self._dst), ctypes.c_int64(self._t),
-                                       ctypes.c_void_p(self.eng.stream_handle())), "mfx_trace_update")
+        check(self._L.mfx_trace_update(ctypes.byref(self._src), ctypes.byref(self._dst), self._t,
+                                       self.eng.stream_handle()), "mfx_trace_update")
         self._t += 1
 
     def _final(self):
@@ -222,9 +203,7 @@ def _hp(env, handle, n):
         import torch
         from .battle import GET_HP
         buf = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
-        dll.mfx_battle_get.restype = ctypes.c_int
-        check(dll.mfx_battle_get(env.game, int(handle.value), GET_HP, ctypes.c_void_p(buf.data_ptr()), max(n, 1)),
-              "mfx_battle_get")
+        check(dll.mfx_battle_get(env.game, int(handle.value), GET_HP, ptr(buf), max(n, 1)), "mfx_battle_get")
         check(dll.mfx_battle_sync(env.game), "mfx_battle_sync")
         return buf[:n].cpu().numpy()
     try:
@@ -248,6 +227,8 @@ def replay(trace, k, render_dir=None, lib=None, episodes=None):
     e = int(trace["envs"][k])
     T, max_steps, placement = trace["steps"], trace["max_steps"], trace["placement"]
     env = magent.GridWorld("battle", map_size=trace["map_size"], lib=lib if lib is not None else magent.load_library())
+    if getattr(env._lib, "dll", None) is not None:
+        bind(env._lib.dll)                               # (_hp calls mfx_battle_get through it)
     h = env.get_handles()
     out_dir = None
     if render_dir is not None:

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import check, lib
+from .abi import ptr, stream, struct
 
 _MAX_COLS = 12
 
@@ -35,17 +36,10 @@ def rows_copy(dst, src, idx=None, src_mod=0, dst_start=0, dst_cap=0, n=None, shi
         idx = idx.to(device=dst[0].device, dtype=torch.int64).contiguous()
     k = len(dst)
     src_rows = min(s.shape[0] for s in src)
-    L = lib()
-    L.mfx_rows_copy.restype = ctypes.c_int
     P = ctypes.c_void_p * k
-    L.mfx_rows_copy_shift.restype = ctypes.c_int
-    check(L.mfx_rows_copy_shift(k, P(*[d.data_ptr() for d in dst]), P(*[s.data_ptr() for s in src]),
-                                (ctypes.c_int64 * k)(*rb), ctypes.c_void_p(idx.data_ptr() if idx is not None else 0),
-                                ctypes.c_int64(int(src_mod)), ctypes.c_int64(int(src_rows)),
-                                ctypes.c_int64(int(dst_start)), ctypes.c_int64(int(dst_cap)), ctypes.c_int64(int(n)),
-                                ctypes.c_uint32(int(shift_mask)), ctypes.c_int64(int(shift)),
-                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-          "mfx_rows_copy_shift")
+    check(lib().mfx_rows_copy_shift(k, P(*[d.data_ptr() for d in dst]), P(*[s.data_ptr() for s in src]),
+                                    (ctypes.c_int64 * k)(*rb), ptr(idx), int(src_mod), int(src_rows), int(dst_start),
+                                    int(dst_cap), int(n), int(shift_mask), int(shift), stream()), "mfx_rows_copy_shift")
 
 
 def rows_plan(dst, src, shift_mask=0):
@@ -56,12 +50,10 @@ def rows_plan(dst, src, shift_mask=0):
     assert len(dst) == len(src) and 0 < len(dst) <= _MAX_COLS
     rb = [d.element_size() * (d[0].numel() if d.dim() > 1 else 1) for d in dst]
     k = len(dst)
-    L = lib()
-    L.mfx_rows_copy_plan.restype = ctypes.c_int
     P = ctypes.c_void_p * k
     out = (ctypes.c_int32 * (4 + k))()
-    check(L.mfx_rows_copy_plan(k, P(*[d.data_ptr() for d in dst]), P(*[s.data_ptr() for s in src]),
-                               (ctypes.c_int64 * k)(*rb), ctypes.c_uint32(int(shift_mask)), out), "mfx_rows_copy_plan")
+    check(lib().mfx_rows_copy_plan(k, P(*[d.data_ptr() for d in dst]), P(*[s.data_ptr() for s in src]),
+                                   (ctypes.c_int64 * k)(*rb), int(shift_mask), out), "mfx_rows_copy_plan")
     return {"form": out[0], "nw": out[1], "nu": out[2], "units": out[3], "cols": list(out[4:4 + k])}
 
 
@@ -71,16 +63,7 @@ def rollout_key(env, episode, agent_id, n_envs, id_stride):
     return (episode * n_envs + env) * id_stride + agent_id
 
 
-class _CollectSrc(ctypes.Structure):      # mfx_collect_src (include/magent_amd.h)
-    _fields_ = ([(k, ctypes.c_void_p) for k in ("view", "feat", "actions", "rewards", "mean", "stats", "counts", "ids",
-                                                  "alive")] +
-                [(k, ctypes.c_int32) for k in ("n_envs", "n_groups", "group", "rowcap", "view_floats", "feat_floats",
-                                               "n_action", "mean_stride")])
-
-
-class _CollectDst(ctypes.Structure):      # mfx_collect_dst
-    _fields_ = ([(k, ctypes.c_void_p) for k in ("obs", "feat", "act", "rew", "term", "prob", "key")] +
-                [("capacity", ctypes.c_int64)])
+_CollectSrc, _CollectDst = struct("mfx_collect_src"), struct("mfx_collect_dst")
 
 
 class CollectOverflow(RuntimeError):
@@ -127,13 +110,7 @@ class RolloutCollector:
         if memory_group._rows is None:
             raise ValueError("RolloutCollector: the buffer has no step rows yet (EpisodesBuffer.prepare() makes them)")
         if memory_group._rows.device != "cpu":
-            L = lib()
-            for fn in ("mfx_collect_reset", "mfx_collect_begin", "mfx_collect_end", "mfx_collect_end_linked",
-                       "mfx_collect_links_reset"):
-                getattr(L, fn).restype = ctypes.c_int
-            if hasattr(L, "mfx_collect_begin_rows"):        # (absent from older builds, which the bench scripts may load)
-                L.mfx_collect_begin_rows.restype = ctypes.c_int
-            self._L = L
+            self._L = lib()
 
     @property
     def linked(self):
@@ -165,16 +142,10 @@ class RolloutCollector:
         return rows.cap if self.capacity is None else min(rows.cap, int(self.capacity))
 
     # ---- device
-    def _buffer(self, name, group=0):
-        p, nb = ctypes.c_void_p(), ctypes.c_size_t()
-        self.eng._check(self.eng._dll.mfx_battle_rollout_buffer(self.eng.game, name.encode(), group, ctypes.byref(p),
-                                                                ctypes.byref(nb)), "rollout_buffer")
-        return p.value
-
     def begin(self):
         eng, rows = self.eng, self.mg._rows
         E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
-        st = ctypes.c_void_p(eng.stream_handle())
+        st = eng.stream_handle()
         fresh = self._bound is None
         if fresh and self.linked and rows.n != 0:
             raise ValueError("RolloutCollector: %d rows pushed by other means are present; they have no links "
@@ -186,16 +157,14 @@ class RolloutCollector:
                 self._scratch = torch.empty(E * rc + 1 + (E + 63) // 64, dtype=torch.int32, device="cuda")
             cap = self._reserve()
             if fresh:
-                check(self._L.mfx_collect_reset(ctypes.c_void_p(self._state.data_ptr()), ctypes.c_int64(rows.n), st),
-                      "mfx_collect_reset")
+                check(self._L.mfx_collect_reset(ptr(self._state), rows.n, st), "mfx_collect_reset")
             if self.linked:
                 slots = E * self.id_stride()
                 if self._last is None or self._last.numel() != slots:
                     self._last = torch.empty(slots, dtype=torch.int64, device="cuda")
                     fresh = True
                 if fresh:
-                    check(self._L.mfx_collect_links_reset(ctypes.c_void_p(self._last.data_ptr()),
-                                                          ctypes.c_int64(slots), st), "mfx_collect_links_reset")
+                    check(self._L.mfx_collect_links_reset(ptr(self._last), slots, st), "mfx_collect_links_reset")
         V = 1
         for x in rows.obs_shape:
             V *= int(x)
@@ -203,18 +172,15 @@ class RolloutCollector:
         for x in rows.feat_shape:
             F *= int(x)
         g = self.group
-        self._src = _CollectSrc(self._buffer("view", g), self._buffer("feature", g), self._buffer("actions"),
-                                self._buffer("rewards"), self._buffer("mean_action"), self._buffer("stats"),
-                                self._buffer("group_num"), self._buffer("ids"), self._buffer("alive"),
+        self._src = _CollectSrc(eng.rollout_buffer("view", g), eng.rollout_buffer("feature", g),
+                                *[eng.rollout_buffer(k) for k in ("actions", "rewards", "mean_action", "stats", "group_num",
+                                                                  "ids", "alive")],
                                 E, G, g, rc, V, F, int(rows.act_n), eng.mean_stride())
         c = rows.cols
-        self._dst = _CollectDst(c["obs"].data_ptr(), c["feat"].data_ptr(), c["act"].data_ptr(), c["rew"].data_ptr(),
-                                c["term"].data_ptr(), c["prob"].data_ptr() if rows.use_mean else None,
-                                c["ids"].data_ptr(), cap)
-        self._links = ((ctypes.c_void_p(self._last.data_ptr()), ctypes.c_void_p(c["prev"].data_ptr()),
-                        ctypes.c_void_p(c["tail"].data_ptr())) if self.linked else None)
-        self._ptrs = (ctypes.c_void_p(self._scratch.data_ptr()), ctypes.c_void_p(self._scratch.data_ptr() + 4 * E * rc),
-                      ctypes.c_void_p(self._state.data_ptr()))
+        self._dst = _CollectDst(ptr(c["obs"]), ptr(c["feat"]), ptr(c["act"]), ptr(c["rew"]), ptr(c["term"]),
+                                ptr(c["prob"]) if rows.use_mean else None, ptr(c["ids"]), cap)
+        self._links = (ptr(self._last), ptr(c["prev"]), ptr(c["tail"])) if self.linked else None
+        self._ptrs = (ptr(self._scratch), ptr(self._scratch) + 4 * E * rc, ptr(self._state))
         P = self.prob_rows
         if P is not None:
             if not rows.use_mean:
@@ -223,8 +189,8 @@ class RolloutCollector:
                     or tuple(P.shape) != (E, rc, int(rows.act_n))):
                 raise ValueError("RolloutCollector: prob_rows must be a contiguous float32 CUDA tensor [%d, %d, %d], got "
                                  "%s %s" % (E, rc, int(rows.act_n), P.dtype, tuple(P.shape)))
-            check(self._L.mfx_collect_begin_rows(ctypes.byref(self._src), ctypes.byref(self._dst),
-                                                 ctypes.c_void_p(P.data_ptr()), *self._ptrs, st), "mfx_collect_begin_rows")
+            check(self._L.mfx_collect_begin_rows(ctypes.byref(self._src), ctypes.byref(self._dst), ptr(P), *self._ptrs, st),
+                  "mfx_collect_begin_rows")
             return
         check(self._L.mfx_collect_begin(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs, st),
               "mfx_collect_begin")
@@ -233,12 +199,11 @@ class RolloutCollector:
         assert self._src is not None, "RolloutCollector.end() without begin()"
         if self._links is not None:
             check(self._L.mfx_collect_end_linked(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs,
-                                                 ctypes.c_int64(self.id_stride()), *self._links,
-                                                 ctypes.c_void_p(self.eng.stream_handle())), "mfx_collect_end_linked")
+                                                 self.id_stride(), *self._links, self.eng.stream_handle()),
+                  "mfx_collect_end_linked")
         else:
             check(self._L.mfx_collect_end(ctypes.byref(self._src), ctypes.byref(self._dst), *self._ptrs,
-                                          ctypes.c_int64(self.id_stride()), ctypes.c_void_p(self.eng.stream_handle())),
-                  "mfx_collect_end")
+                                          self.id_stride(), self.eng.stream_handle()), "mfx_collect_end")
         self._src = None
 
     def discard(self):
@@ -275,12 +240,8 @@ def chain_returns(rew, prev, tails, values, gamma=0.95, numpy1=True):
     values = values.to(torch.float32).contiguous()
     assert len(values) == len(tails)
     L = lib()
-    L.mfx_chain_returns.restype = ctypes.c_int
-    if L.mfx_chain_returns(ctypes.c_void_p(rew.data_ptr()), ctypes.c_void_p(prev.data_ptr()),
-                           ctypes.c_void_p(tails.data_ptr()), ctypes.c_void_p(values.data_ptr()),
-                           ctypes.c_int64(len(tails)), ctypes.c_int64(len(rew)), ctypes.c_double(gamma),
-                           int(bool(numpy1)), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
-        L.mfx_last_error.restype = ctypes.c_char_p
+    if L.mfx_chain_returns(ptr(rew), ptr(prev), ptr(tails), ptr(values), len(tails), len(rew), gamma,
+                           int(bool(numpy1)), stream()) != 0:
         raise IndexError(L.mfx_last_error().decode())
     return rew
 
@@ -300,13 +261,8 @@ def chain_gae(rew, adv, prev, tails, values, gamma=0.95, lam=0.95):
     assert prev.dtype == torch.int64 and prev.is_contiguous() and len(prev) >= n
     tails = tails.to(torch.int64).contiguous()
     L = lib()
-    L.mfx_chain_gae.restype = ctypes.c_int
-    if L.mfx_chain_gae(ctypes.c_void_p(rew.data_ptr()), ctypes.c_void_p(adv.data_ptr()),
-                       ctypes.c_void_p(prev.data_ptr()), ctypes.c_void_p(tails.data_ptr()),
-                       ctypes.c_void_p(values.data_ptr()), ctypes.c_int64(len(tails)), ctypes.c_int64(n),
-                       ctypes.c_double(gamma), ctypes.c_double(lam),
-                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
-        L.mfx_last_error.restype = ctypes.c_char_p
+    if L.mfx_chain_gae(ptr(rew), ptr(adv), ptr(prev), ptr(tails), ptr(values), len(tails), n, gamma, lam,
+                       stream()) != 0:
         raise IndexError(L.mfx_last_error().decode())
     return rew, adv
 
@@ -315,10 +271,7 @@ def adv_normalize(adv):
     """adv <- (adv - mean) / (std + 1e-8) in place on the float32 column `adv` (mfx_adv_normalize: mean and population
     standard deviation in float64, one summation order per length, no atomics); nothing is read back."""
     assert adv.is_cuda and adv.dtype == torch.float32 and adv.is_contiguous()
-    L = lib()
-    L.mfx_adv_normalize.restype = ctypes.c_int
-    check(L.mfx_adv_normalize(ctypes.c_void_p(adv.data_ptr()), ctypes.c_int64(adv.numel()),
-                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "mfx_adv_normalize")
+    check(lib().mfx_adv_normalize(ptr(adv), adv.numel(), stream()), "mfx_adv_normalize")
     return adv
 
 
@@ -358,8 +311,6 @@ def chain_returns_host(rew, prev, tails, values, gamma=0.95, numpy1=True):
 def check_errors():
     """Synchronise the current stream; raise IndexError if a rows_copy since the last check met a source
     index outside its source rows (that row was skipped)."""
-    L = lib()
-    L.mfx_rows_copy_error.restype = ctypes.c_int
     bad = ctypes.c_int64()
-    if L.mfx_rows_copy_error(ctypes.byref(bad), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) != 0:
+    if lib().mfx_rows_copy_error(ctypes.byref(bad), stream()) != 0:
         raise IndexError("rows_copy: source index %d out of range" % bad.value)

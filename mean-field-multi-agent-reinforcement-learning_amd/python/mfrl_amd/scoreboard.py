@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import check, lib
+from .abi import ptr, struct
 
 RECORD = np.dtype([("len", np.int32), ("nums", np.int32, 2), ("surv", np.int32, 2), ("kill", np.int32, 2),
                    ("winner", np.int32), ("ret", np.float64, 2)])          # mfx_score_record
@@ -37,21 +38,8 @@ class ScoreError(RuntimeError):
     pass
 
 
-class _ScoreSrc(ctypes.Structure):        # mfx_score_src (include/magent_amd.h)
-    _fields_ = ([(k, ctypes.c_void_p) for k in ("group_num", "alive", "stats", "agent_steps")] +
-                [(k, ctypes.c_int32) for k in ("n_envs", "n_groups", "rowcap")])
-
-
-class _ScoreDst(ctypes.Structure):        # mfx_score_dst
-    _fields_ = ([(k, ctypes.c_void_p) for k in ("carry", "ret0", "totals", "log", "state")] +
-                [(k, ctypes.c_int64) for k in ("ep_cap", "target")])
-
-
-def score_lib():
-    L = lib()
-    for fn in ("mfx_score_attach", "mfx_score_update", "mfx_score_sizes"):
-        getattr(L, fn).restype = ctypes.c_int
-    return L
+_ScoreSrc, _ScoreDst = struct("mfx_score_src"), struct("mfx_score_dst")
+score_lib = lib                         # (the name the kernel tests reach the library by)
 
 
 def error_text(word):
@@ -68,41 +56,35 @@ class RolloutScoreboard:
         if len(eng.handles) != 2:
             raise ValueError("RolloutScoreboard: two groups only (main and opponent), got %d" % len(eng.handles))
         self.eng, self.ep_cap, self.target = eng, int(ep_cap), int(target)
-        self._L = score_lib()
+        self._L = lib()
         self._bufs = self._src = self._dst = None
         self._shape = None
-
-    def _buffer(self, name):
-        p, nb = ctypes.c_void_p(), ctypes.c_size_t()
-        self.eng._check(self.eng._dll.mfx_battle_rollout_buffer(self.eng.game, name.encode(), 0, ctypes.byref(p),
-                                                                ctypes.byref(nb)), "rollout_buffer")
-        return p.value
 
     def _structs(self):
         eng = self.eng
         E, rc = eng.n_envs, eng.rowcap
         if self._shape != (E, self.ep_cap):
             sizes = (ctypes.c_size_t * 5)()
-            check(self._L.mfx_score_sizes(E, ctypes.c_int64(self.ep_cap), sizes), "mfx_score_sizes")
+            check(self._L.mfx_score_sizes(E, self.ep_cap, sizes), "mfx_score_sizes")
             with torch.cuda.stream(eng.torch_stream()):
                 self._bufs = [torch.zeros(max(int(n), 8) // 8, dtype=torch.int64, device="cuda") for n in sizes]
             self._shape = (E, self.ep_cap)
         # (the rollout buffers may move at a rollout_init: their addresses are taken again at every attach)
-        self._src = _ScoreSrc(self._buffer("group_num"), self._buffer("alive"), self._buffer("stats"),
-                              self._buffer("agent_steps"), E, len(eng.handles), rc)
-        self._dst = _ScoreDst(*[b.data_ptr() for b in self._bufs], self.ep_cap, self.target)
+        self._src = _ScoreSrc(*[eng.rollout_buffer(k) for k in ("group_num", "alive", "stats", "agent_steps")], E,
+                              len(eng.handles), rc)
+        self._dst = _ScoreDst(*[ptr(b) for b in self._bufs], self.ep_cap, self.target)
 
     def attach(self):
         """After rollout_policy_observe, before the first policy step of the round."""
         self._structs()
-        check(self._L.mfx_score_attach(ctypes.byref(self._src), ctypes.byref(self._dst),
-                                       ctypes.c_void_p(self.eng.stream_handle())), "mfx_score_attach")
+        check(self._L.mfx_score_attach(ctypes.byref(self._src), ctypes.byref(self._dst), self.eng.stream_handle()),
+              "mfx_score_attach")
 
     def update(self):
         """After every rollout_policy_step, exactly once."""
         assert self._src is not None, "RolloutScoreboard.update() before attach()"
-        check(self._L.mfx_score_update(ctypes.byref(self._src), ctypes.byref(self._dst),
-                                       ctypes.c_void_p(self.eng.stream_handle())), "mfx_score_update")
+        check(self._L.mfx_score_update(ctypes.byref(self._src), ctypes.byref(self._dst), self.eng.stream_handle()),
+              "mfx_score_update")
 
     def reached(self):
         """Envs that have finished `target` episodes since attach(): an 8-byte readback behind the engine's stream."""
