@@ -446,7 +446,8 @@ int mfx_acnet_destroy(void *handle);
 int mfx_acnet_set_weights(void *handle, const float *d_blob, size_t n_floats, void *stream);
 /* The view inputs that can be non-zero, mask[n] (n = view_floats; e.g. mfx_battle_view_support), or null for the dense
  * order: later forwards run the view layer over the supported inputs only, bit-identical when the others are zero
- * (the caller's contract).  input_support_size: the inputs the view layer runs over (0 = dense). */
+ * (the caller's contract).  A mask with n != view_floats is refused and leaves the handle's support as it was.
+ * input_support_size: the inputs the view layer runs over (0 = dense). */
 int mfx_acnet_set_input_support(void *handle, const uint8_t *mask, int n, void *stream);
 int mfx_acnet_input_support_size(void *handle, int *k);
 /* Acting precision of mfx_acnet_forward / mfx_acnet_act_rollout: 0 = f32 (the default at create), 1 = bf16, the

@@ -289,18 +289,17 @@ class ActorCritic:
     def act_rollout(self, eng, group, prob_rows=None):
         """Sampled actions of group `group` of a BattleBatch's rollout from its observation buffers into its action
         buffer (mfrl_amd.policy.ACNetHIP.act_rollout) with the current weights and the draw of act_dev (self.seed,
-        the act count); nothing is read back.  The weights are uploaded on the caller's current stream: when they
-        moved and the engine sits on another stream, the engine's stream waits for the upload.  prob_rows (the mean
+        the act count); nothing is read back.  Streams: the weights -- however they moved: an optimiser step,
+        load_state_dict, a "hip"-backend step, which hands its blob to the acting handle itself -- a mode's first
+        images and the support image are enqueued on the caller's current stream, the kernels on the engine's.  The
+        handle orders the two (mfrl_amd.policy.StreamOrder): every engine that acts with this model, on whatever
+        stream, waits for the handle's last change once, the first time it acts after it.  prob_rows (the mean
         action per agent of mean_field = "neighbors") is accepted and not read: the policy head takes no mean action,
         only the value head does, in training, from the collected rows."""
         if not self._hip_ok():
             raise ValueError("act_rollout: the HIP forward takes 2..32 actions, views of at most 4096 floats and at "
                              "most 256 features")
-        before = (self._hip_key, self._hip.precision if self._hip is not None else None)
         hip = self._hip_net(self.act_precision)
-        # (the upload and a mode's first images both run on the current stream)
-        if (self._hip_key, hip.precision) != before and eng.stream_handle() != torch.cuda.current_stream().cuda_stream:
-            eng.torch_stream().wait_stream(torch.cuda.current_stream())
         self._draws += 1
         hip.act_rollout(eng, group, seed=self.seed, step=self._draws)
 
@@ -357,11 +356,14 @@ class ActorCritic:
             value, adv = self._gae_columns(rows.cap)
             value.record_stream(col.eng.torch_stream())
             adv.record_stream(col.eng.torch_stream())
+        # the f32 handle with the current weights, taken on the caller's stream: an upload reads the parameters where
+        # torch last wrote them, and the handle orders the engine's stream -- and every other engine's -- behind it
+        hip = self._hip_net() if self._hip_ok() else None
         with torch.cuda.stream(col.eng.torch_stream()), torch.no_grad():
             tails = c["tail"][:n].nonzero().reshape(-1)
             if gae:
                 # the f32 value of every row (whatever act_precision is), then the walk along the same chains
-                _, v_rows, _ = self._hip_net().forward(c["obs"][:n], c["feat"][:n], prob[:n] if prob is not None else None,
+                _, v_rows, _ = hip.forward(c["obs"][:n], c["feat"][:n], prob[:n] if prob is not None else None,
                                                        want_policy=False, want_value=True, want_act=False)
                 value[:n].copy_(v_rows.reshape(-1))
                 replay.chain_gae(c["rew"][:n], adv, c["prev"], tails, value, self.gamma, self._gae_lambda)
@@ -369,8 +371,8 @@ class ActorCritic:
                     replay.adv_normalize(adv[:n])
             else:
                 p_t = prob[tails] if prob is not None else None
-                if self._hip_ok():
-                    _, keep, _ = self._hip_net().forward(c["obs"][tails], c["feat"][tails], p_t, want_policy=False,
+                if hip is not None:
+                    _, keep, _ = hip.forward(c["obs"][tails], c["feat"][tails], p_t, want_policy=False,
                                                          want_value=True, want_act=False)
                 else:
                     _, keep = self.net(c["obs"][tails], c["feat"][tails], p_t)

@@ -367,8 +367,10 @@ class ValueNet:
     def act_rollout(self, eng, group, eps=None, prob_rows=None):
         """Greedy actions of group `group` of a BattleBatch's rollout from its observation buffers into its action
         buffer (mfrl_amd.policy.QNetHIP.act_rollout), with the eval net's current weights; nothing is read back.
-        The weights are uploaded on the caller's current stream: when they moved and the engine sits on another
-        stream, the engine's stream waits for the upload.
+        Streams: the weights -- however they moved: an optimiser step, load_state_dict, train_batches of either
+        backend -- are packed and uploaded on the caller's current stream, which is where torch wrote them; the
+        kernels run on the engine's.  The handle orders the two (mfrl_amd.policy.StreamOrder): every engine that acts
+        with this model, on whatever stream, waits for the last upload once, the first time it acts after it.
 
         explore = "boltzmann": row j of env e is drawn from softmax(q / eps) with the uniform (self.seed, the count
         of acting calls, group, e * rowcap + j); eps None: self.temperature (the last eps, 0.1 at first).  With the
@@ -378,10 +380,7 @@ class ValueNet:
         (mean_field = "neighbors": mfrl_amd.mf.NeighborMean.rows), handed to QNetHIP.act_rollout."""
         if not (self.view_space == (13, 13, 7) and self.num_actions <= 32):
             raise ValueError("act_rollout: the HIP forward takes the Battle view (13, 13, 7) and at most 32 actions")
-        before = self._hip_key
         hip = self._hip_current()
-        if self._hip_key != before and eng.stream_handle() != torch.cuda.current_stream().cuda_stream:
-            eng.torch_stream().wait_stream(torch.cuda.current_stream())
         if self._explore == "boltzmann":
             if eps is not None:
                 self.temperature = eps

@@ -68,6 +68,50 @@ def _rollout_args(scratch, eng, group, names):
     return bufs, rows.data_ptr(), rows.data_ptr() + 4 * E * rc
 
 
+def _record_event(ts):
+    ev = torch.cuda.Event()
+    ev.record(ts)
+    return ev
+
+
+class StreamOrder:
+    """Which streams have seen a handle's current device state (DESIGN "streams").  The contract it keeps for QNetHIP /
+    ACNetHIP: after load, set_blob, set_precision or set_input_support returns, a later forward / act_rollout of that
+    handle on *any* stream reads the new state.  (Only that direction: an upload does not wait for act kernels still
+    pending on another stream that read the state it overwrites -- synchronise those before uploading, as the shipped
+    loops do with finish().)
+
+    produced(sid, ts): state was enqueued on stream `ts` (id `sid`: its hipStream_t).  A new generation begins; only
+    that stream has seen it.  ready(sid, ts): make the state visible on stream `sid` -- at a stream's first use in a
+    generation an event is recorded on the producer's stream (once per generation, and only if a foreign stream ever
+    asks) and the consumer's stream waits for it.  After that, and always for the producer's own stream, the call is a
+    set lookup: no event is recorded or waited for.  A producer that reads the state it extends (the support image
+    gathers from the blob) calls ready() for its own stream first, so the order is transitive.
+    record(stream) -> event and wait(stream, event) are torch's by default; tests pass fakes."""
+
+    def __init__(self, record=_record_event, wait=lambda ts, ev: ts.wait_event(ev)):
+        self.gen = 0
+        self.seen = set()           # stream ids ordered after the current generation's producer
+        self._producer = None       # the stream object the current generation was enqueued on
+        self._event = None          # recorded on it, at the first foreign consumer
+        self._record, self._wait = record, wait
+
+    def produced(self, sid, ts):
+        self.gen += 1
+        self._producer, self._event = ts, None
+        self.seen = {sid}
+
+    def ready(self, sid, ts):
+        """-> True when stream `sid` had to wait.  ts: the stream object, or a callable giving it (called only then)."""
+        if sid in self.seen or self._producer is None:
+            return False
+        if self._event is None:
+            self._event = self._record(self._producer)
+        self._wait(ts() if callable(ts) else ts, self._event)
+        self.seen.add(sid)
+        return True
+
+
 PRECISIONS = {"f32": 0, "bf16": 1}      # mfx_qnet_set_precision / mfx_acnet_set_precision
 
 N_BLOCKS = 18      # w1 b1 w2 b2 wd bd we be wp1 bp1 wp2 bp2 w2d b2d wo bo wq bq (policy_kernels.hip)
@@ -174,6 +218,7 @@ class QNetHIP:
               "mfx_qnet_create")
         self.handle = hdl
         self._rows = {}
+        self._order = StreamOrder()
         if precision != "f32":
             check(L.mfx_qnet_set_precision(hdl, PRECISIONS[precision], None), "mfx_qnet_set_precision")
 
@@ -186,9 +231,12 @@ class QNetHIP:
         return pack_qnet(net, self.F, self.A, self.use_mf, (self.blob_n, self.offsets))
 
     def load(self, net):
-        """Upload the weights of torch QNet `net` (same shapes)."""
+        """Upload the weights of torch QNet `net` (same shapes), on the current stream.  Every later forward /
+        act_rollout of this handle, on any stream, reads them (StreamOrder)."""
         self._blob = self.pack(net).contiguous()
-        check(self._L.mfx_qnet_set_weights(self.handle, ptr(self._blob), self.blob_n, stream()), "mfx_qnet_set_weights")
+        sid = stream()
+        check(self._L.mfx_qnet_set_weights(self.handle, ptr(self._blob), self.blob_n, sid), "mfx_qnet_set_weights")
+        self._order.produced(sid, torch.cuda.current_stream())
         return self
 
     # ------------------------------------------------------------------ forward
@@ -202,6 +250,9 @@ class QNetHIP:
         third result.  A temperature that is not finite and > 0 raises (nothing is launched)."""
         if temperature is None and want_w:
             raise ValueError("QNetHIP.forward: want_w needs a temperature")
+        sid = stream()
+        if sid not in self._order.seen:                 # (the weights were uploaded on another stream)
+            self._order.ready(sid, torch.cuda.current_stream)
         n = view.shape[0]
         view = view.reshape(n, -1).contiguous().float()
         feature = feature.reshape(n, -1).contiguous().float()
@@ -214,10 +265,10 @@ class QNetHIP:
             w = torch.empty((n, self.A), dtype=torch.float32, device=view.device) if want_w else None
             check(self._L.mfx_qnet_forward_sample(self.handle, ptr(view), ptr(feature),
                                                   ptr(prob if self.use_mf else None), int(n), ptr(q), ptr(w), ptr(act),
-                                                  temperature, seed, step, stream()), "mfx_qnet_forward_sample")
+                                                  temperature, seed, step, sid), "mfx_qnet_forward_sample")
             return (q, act, w) if want_w else (q, act)
         check(self._L.mfx_qnet_forward(self.handle, ptr(view), ptr(feature), ptr(prob if self.use_mf else None),
-                                       int(n), ptr(q), ptr(act), stream()), "mfx_qnet_forward")
+                                       int(n), ptr(q), ptr(act), sid), "mfx_qnet_forward")
         return q, act
 
     def act(self, view, feature, prob=None, temperature=None, seed=0, step=0):
@@ -231,6 +282,11 @@ class QNetHIP:
         prob_rows (None: the rollout's mean action of the env, one row per (env, group)): a float32 CUDA tensor
         [E, rowcap, A], contiguous -- row j of env e reads its own mean action prob_rows[e, j] (the neighbourhood mean,
         mfrl_amd.mf.NeighborMean.rows); it must be ready on the engine's stream.
+
+        Streams: the kernels run on the engine's stream.  The weights may have been uploaded (load) on any other
+        stream: the engine's stream waits for that upload the first time it uses the handle afterwards -- every engine
+        that shares the handle does, each once per upload (StreamOrder); later calls, and an engine on the uploading
+        stream, wait for nothing.  The observation buffers and prob_rows are the caller's to order.
 
         Works on every plan that takes a learned policy (BattleBatch.rollout_policy_path: all but
         MFX_ROLLOUT_PIPE=1 -- large batches, large envs and few-env batches alike; E, rowcap and the buffers come
@@ -252,10 +308,13 @@ class QNetHIP:
                 rows, total, buf["actions"])
         if temperature is not None:
             args += (temperature, seed, step)
+        sid = eng.stream_handle()
+        if sid not in self._order.seen:
+            self._order.ready(sid, eng.torch_stream)
         fn = {(False, False): "mfx_qnet_act_rollout", (False, True): "mfx_qnet_act_rollout_sample",
               (True, False): "mfx_qnet_act_rollout_rows", (True, True): "mfx_qnet_act_rollout_rows_sample"}[
                   (prob_rows is not None, temperature is not None)]
-        check(getattr(self._L, fn)(*args, eng.stream_handle()), fn)
+        check(getattr(self._L, fn)(*args, sid), fn)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -378,6 +437,7 @@ class ACNetHIP:
         self.handle = hdl
         self._rows = {}
         self._support = None
+        self._order = StreamOrder()
         if precision != "f32":
             check(L.mfx_acnet_set_precision(hdl, PRECISIONS[precision], None), "mfx_acnet_set_precision")
 
@@ -390,9 +450,15 @@ class ACNetHIP:
         return pack_acnet(net, self.V, self.F, self.A, self.use_mf, (self.blob_n, self.offsets))
 
     def load(self, net):
-        """Upload the weights of torch ACNet `net` (same shapes)."""
+        """Upload the weights of torch ACNet `net` (same shapes), on the current stream.  Every later forward /
+        act_rollout of this handle, on any stream, reads them (StreamOrder)."""
         self._blob = self.pack(net).contiguous()
-        check(self._L.mfx_acnet_set_weights(self.handle, ptr(self._blob), self.blob_n, stream()), "mfx_acnet_set_weights")
+        return self._upload()
+
+    def _upload(self):
+        sid = stream()
+        check(self._L.mfx_acnet_set_weights(self.handle, ptr(self._blob), self.blob_n, sid), "mfx_acnet_set_weights")
+        self._order.produced(sid, torch.cuda.current_stream())
         return self
 
     def set_blob(self, blob):
@@ -400,8 +466,7 @@ class ACNetHIP:
         a device-to-device copy, no packing."""
         assert blob.is_cuda and blob.dtype == torch.float32 and blob.numel() == self.blob_n
         self._blob = blob.contiguous()
-        check(self._L.mfx_acnet_set_weights(self.handle, ptr(self._blob), self.blob_n, stream()), "mfx_acnet_set_weights")
-        return self
+        return self._upload()
 
     def set_precision(self, precision):
         """Switch the handle's mode (mfx_acnet_set_precision): the f32 weights stay, the images the mode lacks are
@@ -409,10 +474,19 @@ class ACNetHIP:
         if precision not in PRECISIONS:
             raise ValueError("ACNetHIP: precision %r (one of %s)" % (precision, ", ".join(PRECISIONS)))
         if precision != self.precision:
-            check(self._L.mfx_acnet_set_precision(self.handle, PRECISIONS[precision], stream()),
-                  "mfx_acnet_set_precision")
+            sid = self._extend()
+            check(self._L.mfx_acnet_set_precision(self.handle, PRECISIONS[precision], sid), "mfx_acnet_set_precision")
+            self._order.produced(sid, torch.cuda.current_stream())
             self.precision = precision
         return self
+
+    def _extend(self):
+        """The current stream's id, ordered after the handle's state: what a call that builds images from the weights
+        (a mode's first images, the support image) starts with, before it becomes the state's producer itself."""
+        sid = stream()
+        if sid not in self._order.seen:
+            self._order.ready(sid, torch.cuda.current_stream)
+        return sid
 
     def set_input_support(self, mask):
         """mask: uint8/bool [V], 1 where the view can be non-zero (e.g. BattleBatch.view_support), or None for the
@@ -423,8 +497,17 @@ class ACNetHIP:
             self._support = None
             return self
         m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8).reshape(-1))
-        check(self._L.mfx_acnet_set_input_support(self.handle, ptr(m), int(m.size), stream()),
-              "mfx_acnet_set_input_support")
+        sid = self._extend()
+        try:
+            check(self._L.mfx_acnet_set_input_support(self.handle, ptr(m), int(m.size), sid),
+                  "mfx_acnet_set_input_support")
+        except Exception:
+            # a mask of the wrong size leaves the handle and self._support as they were; a support whose packed chunks
+            # span too far is refused with the old one already freed: the handle is back on the dense order
+            if self.input_support_size() == 0:
+                self._support = None
+            raise
+        self._order.produced(sid, torch.cuda.current_stream())
         self._support = m.copy()
         return self
 
@@ -440,6 +523,7 @@ class ACNetHIP:
         group 0, row i)).  precision="bf16" is acting only: want_value raises ValueError."""
         if want_value and self.precision != "f32":
             raise ValueError("ACNetHIP: precision %r is acting only (no value head)" % self.precision)
+        sid = self._extend()
         n = view.shape[0]
         view = view.reshape(n, -1).contiguous().float()
         feature = feature.reshape(n, -1).contiguous().float()
@@ -453,7 +537,7 @@ class ACNetHIP:
         val = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
         act = torch.empty(n, dtype=torch.int32, device=dev) if want_act else None
         check(self._L.mfx_acnet_forward(self.handle, ptr(view), ptr(feature), ptr(prob), int(n), ptr(pol), ptr(val),
-                                        ptr(act), seed, step, stream()), "mfx_acnet_forward")
+                                        ptr(act), seed, step, sid), "mfx_acnet_forward")
         return pol, val, act
 
     def act(self, view, feature, seed=0, step=0):
@@ -464,7 +548,13 @@ class ACNetHIP:
         written into the rollout's action buffer [E][G][rowcap] (live rows; row j of env e drawn with (seed,
         step, group, e * rowcap + j)).  Nothing is read back to the host.  support: run the view layer over the
         inputs the engine's view can make non-zero only (BattleBatch.view_support; bit-identical).  The row-list
-        scratch is per engine, so engines on different streams may share this network."""
+        scratch is per engine, so engines on different streams may share this network.
+
+        Streams: the kernels run on the engine's stream.  The weights, a mode's images and the support image --
+        built by this very call, on the current stream, when the support is not the handle's yet -- may come from any
+        other stream: the engine's stream waits for them the first time it uses the handle afterwards, every engine
+        that shares the handle each once (StreamOrder); later calls, and an engine on the producing stream, wait for
+        nothing."""
         E, rc, G = eng.n_envs, eng.rowcap, len(eng.handles)
         if support:
             m = eng.view_support(group)
@@ -473,9 +563,12 @@ class ACNetHIP:
         elif self._support is not None:
             self.set_input_support(None)
         buf, rows, total = _rollout_args(self._rows, eng, group, ("view", "feature", "group_num", "actions"))
+        sid = eng.stream_handle()
+        if sid not in self._order.seen:
+            self._order.ready(sid, eng.torch_stream)
         check(self._L.mfx_acnet_act_rollout(self.handle, buf["view"], buf["feature"], buf["group_num"], int(E), int(G),
-                                            int(group), int(rc), rows, total, buf["actions"], seed, step,
-                                            eng.stream_handle()), "mfx_acnet_act_rollout")
+                                            int(group), int(rc), rows, total, buf["actions"], seed, step, sid),
+              "mfx_acnet_act_rollout")
 
 
 # ---------------------------------------------------------------------------------------------------------------
