@@ -99,6 +99,38 @@ def forest(value_scale=1.0):
     return out
 
 
+def _made(key, prev, tails, rows, rng, value_scale=1.0):
+    out = {"rew": rng.standard_normal(len(prev)).astype(np.float32), "prev": prev, "tails": tails, "rows": rows,
+           "V": (value_scale * rng.standard_normal(len(prev))).astype(np.float32)}
+    for k in ("rew", "prev", "tails", "V"):
+        out[k].setflags(write=False)
+    _FOREST[key] = out
+    return out
+
+
+def short_forest(n_tails):
+    """n_tails interleaved chains of 1..3 rows, every length present (256 tails: k_chain_gae's one full workgroup; 257:
+    one lane in a second).  Shared, read-only."""
+    key = ("short", n_tails)
+    if key in _FOREST:
+        return _FOREST[key]
+    rng = np.random.default_rng(FOREST_SEED + n_tails)
+    lens = rng.integers(1, 4, size=n_tails)
+    prev, tails, rows = _forest(rng, lens)
+    assert len(tails) == n_tails and set(lens.tolist()) == {1, 2, 3}
+    return _made(key, prev, tails, rows, rng)
+
+
+def long_chain(n=5000):
+    """One chain over all n rows (prev[r] = r - 1), for the walk at gamma = lambda = 1.  Shared, read-only."""
+    key = ("long", n)
+    if key in _FOREST:
+        return _FOREST[key]
+    rng = np.random.default_rng(FOREST_SEED + n)
+    prev = np.arange(-1, n - 1, dtype=np.int64)
+    return _made(key, prev, np.array([n - 1], np.int64), [np.arange(n)], rng)
+
+
 def torch_gradient(net, rows, adv, dtype, device="cpu", value_coef=ar.VALUE_COEF, ent_coef=ar.ENT_COEF):
     """actrain_ref.torch_gradient with the policy term's advantage taken from the column `adv` (None: ret - value,
     detached -- the default loss): (named gradients as float64 numpy, (pg, vf, ent, mean value))."""

@@ -208,3 +208,19 @@ class QRef:
 @functools.lru_cache(maxsize=None)
 def qnet_case(F, A, use_mf, bf16=False):
     return QRef(F, A, use_mf, bf16)
+
+
+# ------------------------------------------------------------------------------------------------- the Boltzmann target
+QTRAIN_SOFT_T = (1.0, 0.1)
+
+
+def qtrain_soft_target64(eb64, tb64, off, F, A, use_mf, ring, n_ring, idx, gamma, T):
+    """The float64 Boltzmann target (qtarget_ref.target64) of ring rows idx from the float64 forwards of both nets on
+    the next rows: tests/test_qtarget_gpu.py's yardstick at another (F, A).  -> (y, eval Q, target Q of the next rows)."""
+    import qtarget_ref as qt
+    qt.check(A, T)
+    nxt = (np.asarray(idx) + 1) % n_ring
+    pn = ring["prob"][nxt] if use_mf else None
+    q_e = qnet_ref.forward(eb64, off, F, A, use_mf, ring["obs"][nxt], ring["feat"][nxt], pn)
+    q_t = qnet_ref.forward(tb64, off, F, A, use_mf, ring["obs"][nxt], ring["feat"][nxt], pn)
+    return qt.target64(q_e, q_t, ring["rew"][idx], ring["term"][idx], gamma, T), q_e, q_t

@@ -98,3 +98,33 @@ def test_battle_view_support_without_gpu(built):
         assert int(m.sum()) == 903
     bad = np.zeros(10, dtype=np.uint8)
     assert dll.mfx_battle_view_support(env.game, 0, bad.ctypes.data_as(ctypes.c_void_p), bad.size) != 0
+
+
+def _support_game(name):
+    from test_rules_gpu import check_support, support_games, support_masks
+    config, map_size, play = support_games()[name]
+    return name, play, check_support, support_masks(config, map_size)
+
+
+def _support_names():
+    from test_rules_gpu import SUPPORT_GAMES
+    return SUPPORT_GAMES
+
+
+@pytest.mark.skipif(not os.path.exists(common.REF_LIB), reason="oracle/_ref not built")
+@pytest.mark.parametrize("name", _support_names())
+def test_view_support_covers_the_reference_observation(built, name):
+    """The CPU twin of tests/test_rules_gpu.py::test_view_support_covers_the_observation: the same games played on the
+    reference build (whose observations that module holds the engine to, bit for bit), every view row of every step
+    exactly zero outside the mask mfx_battle_view_support gives for the config -- other view ranges, bodies larger
+    than 1 x 1, turn mode, minimap off -- and the mask not all ones where the view range is a circle."""
+    name, play, check, masks = _support_game(name)
+    assert check(name, play(common.REF_LIB), masks) > 100
+
+
+def test_view_support_covers_the_oracle_observation(built):
+    """The same for the generic rollout config (11 x 11 view, no minimap) on the C oracle, which needs no reference
+    build."""
+    name, play, check, masks = _support_game("generic")
+    assert check(name, play(common.ORACLE_LIB), masks) > 100
+    assert masks[0][0].shape[:2] == (11, 11)

@@ -5,10 +5,14 @@ The walk and the normalisation straight through the C ABI against tests/gae_ref.
 valid memory.  The loss head with an advantage column against torch in float64, torch's own f32 error as the yardstick
 (tests/test_actrain_gpu.py's margin).  End to end on rows a linked collector left ("few" plan, 25 scripted steps):
 train_rollout under "gae" on both backends, lambda = 1 against the default loss, and a model set to "gae" and back.
-Driver: two rounds of play_rollout_episodes under "gae" + adv_norm."""
+Driver: two rounds of play_rollout_episodes under "gae" + adv_norm.
+
+ACTRAIN_ERROR_OUT=<path>: test_adv_normalize and the loss-head tests append their measured figures there
+(profiles/gae_shapes_error.jsonl is such a run)."""
 import copy
 import ctypes
 import json
+import os
 
 import numpy as np
 import pytest
@@ -46,7 +50,9 @@ def _gae_call(dll, rew, adv, prev, tails, V, lam, gamma=GAMMA):
 # ------------------------------------------------------------------------------------------------- the walk
 @pytest.mark.parametrize("lam", LAMBDAS)
 def test_chain_gae_equals_the_restatement(lam):
-    """Zero tails: nothing is written; one chain of one row; the forest (301 tails: two workgroups; a chain of 400)."""
+    """Zero tails: nothing is written; one chain of one row; the forest (301 tails: two workgroups; a chain of 400);
+    forests of exactly 256 and 257 tails with chains of 1..3 rows (one full workgroup; one lane in a second); at
+    lambda = 1 one chain of 5000 rows with gamma = 1 (gl = 1: nothing decays over the whole walk)."""
     dll = _abi()
     rng = np.random.default_rng(29)
     rew = rng.standard_normal(5).astype(np.float32)
@@ -56,11 +62,15 @@ def test_chain_gae_equals_the_restatement(lam):
     assert rc == 0 and out.tobytes() == rew.tobytes() and adv.tobytes() == sent.tobytes()
     one = {"rew": np.array([0.75], np.float32), "prev": np.array([-1], np.int64), "tails": np.array([0], np.int64),
            "V": np.array([-1.25], np.float32)}
-    for f in (one, gae_ref.forest(1.0), gae_ref.forest(100.0)):
+    cases = [(f, GAMMA) for f in (one, gae_ref.forest(1.0), gae_ref.forest(100.0), gae_ref.short_forest(256),
+                                  gae_ref.short_forest(257))]
+    if lam == 1.0:
+        cases.append((gae_ref.long_chain(), 1.0))
+    for f, gamma in cases:
         sent = np.full(len(f["rew"]), -7, np.float32)
-        want_rew, want_adv, bad = gae_ref.chain_gae(f["rew"], f["prev"], f["tails"], f["V"], GAMMA, lam, adv=sent)
+        want_rew, want_adv, bad = gae_ref.chain_gae(f["rew"], f["prev"], f["tails"], f["V"], gamma, lam, adv=sent)
         assert bad is None
-        rc, out, adv = _gae_call(dll, f["rew"], sent, f["prev"], f["tails"], f["V"], lam)
+        rc, out, adv = _gae_call(dll, f["rew"], sent, f["prev"], f["tails"], f["V"], lam, gamma=gamma)
         assert rc == 0
         assert adv.tobytes() == want_adv.tobytes() and out.tobytes() == want_rew.tobytes(), len(f["rew"])
         assert (adv != -7).all()                               # every row of the forest is on a chain
@@ -125,11 +135,13 @@ def test_the_wrapper_raises_index_error():
 
 
 # ------------------------------------------------------------------------------------------------- the normalisation
-@pytest.mark.parametrize("n", [1, 255, 256, 257, 70001])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 70001, 4096, 4097, 4194304, 4194305])
 def test_adv_normalize(n):
     """Two calls on equal input: bitwise equal output; within one float32 spacing of the numpy float64 result (whose
     summation order is another: the difference before the rounding to float32 is of the order of n 2^-53); a constant
-    column becomes zeros."""
+    column becomes zeros.  The partition's edges: 4096 is one part, 4097 two parts of 2049, 4194304 the full 1024 parts
+    of 4096 and 4194305 the cap, 1024 parts of 4097 (n 2^-53 is 5e-10 there, still far inside one spacing).
+    ACTRAIN_ERROR_OUT=<path>: the measured max err / spacing is appended there."""
     import torch
     dll = _abi()
     st = P(torch.cuda.current_stream().cuda_stream)
@@ -143,7 +155,11 @@ def test_adv_normalize(n):
     want = gae_ref.adv_normalize(a)
     w32 = want.astype(np.float32)
     err = np.abs(outs[0].astype(np.float64) - want)
-    print("n", n, "max err / spacing", float((err / np.spacing(np.abs(w32)).astype(np.float64)).max()) if n > 1 else 0.0)
+    worst = float((err / np.spacing(np.abs(w32)).astype(np.float64)).max()) if n > 1 else 0.0
+    print("n", n, "max err / spacing", worst)
+    if os.environ.get("ACTRAIN_ERROR_OUT"):
+        with open(os.environ["ACTRAIN_ERROR_OUT"], "a") as f:
+            f.write(json.dumps({"tag": "adv_normalize", "n": n, "max_err_over_spacing": worst}) + "\n")
     assert (err <= np.spacing(np.abs(w32)).astype(np.float64)).all()
     if n > 1:
         assert abs(float(outs[0].astype(np.float64).mean())) < 1e-6 and abs(float(outs[0].astype(np.float64).std()) - 1) < 1e-5
@@ -153,18 +169,14 @@ def test_adv_normalize(n):
 
 
 # ------------------------------------------------------------------------------------------------- the loss head
-@pytest.mark.parametrize("use_mf", [False, True], ids=["ac", "mfac"])
-def test_loss_head_with_an_advantage_column(use_mf):
-    """ACTrainHIP.grads with an adv column at the Battle shape: 300 rows at chunk_rows = 128 -- three chunks, the last
-    ragged (44 rows), so the column is read at each chunk's row offset and the stats add up over the workgroups of
-    several k_at_loss launches; 300 rows are more than one workgroup's 256.  Per block of the blob e = max |g - g64| /
-    max |g64| against the same loss in torch float64; e_hip <= 4 e_torch, torch's own f32 gradient of that loss.  Then
-    adv = None on the same handle: bitwise a fresh handle's default gradient."""
+def _loss_head(case, seed, n, chunk):
+    """Per block of the blob e = max |g - g64| / max |g64| of ACTrainHIP.grads with an adv column against the same loss
+    in torch float64; e_hip <= 4 e_torch, torch's own f32 gradient of that loss.  Then adv = None on the same handle:
+    bitwise a fresh handle's default gradient.  ACTRAIN_ERROR_OUT=<path>: the figures are appended there."""
     import torch
     import actrain_ref as ar
     from test_actrain_gpu import dev_rows, handle, same_bits
-    V, F, A = ar.BATTLE
-    case, seed, n, chunk = (V, F, A, use_mf), 11, 300, 128
+    V, F, A, use_mf = case
     rows = ar.rows(V, F, A, use_mf, seed, n)
     adv = (2.5 * np.random.RandomState(77).randn(n)).astype(np.float32)
     _, (nb, off) = ar.packed(V, F, A, use_mf, seed)
@@ -179,8 +191,13 @@ def test_loss_head_with_an_advantage_column(use_mf):
     tr.check_error()
     g, stats = g.cpu().numpy(), stats.cpu().numpy()
     e_hip, e_torch = ar.block_errors(g, g64, off, nb), ar.block_errors(g32, g64, off, nb)
-    print(json.dumps({"use_mf": use_mf, "e_hip": [e[0] for e in e_hip], "e_torch": [e[0] for e in e_torch],
-                      "stats": [float(x) for x in stats], "stats64": list(stats64)}))
+    rec = {"tag": "adv-column", "V": V, "F": F, "A": A, "use_mf": use_mf, "n": n, "e_hip": [e[0] for e in e_hip],
+           "e_torch": [e[0] for e in e_torch], "stats": [float(x) for x in stats], "stats64": list(stats64),
+           "max_ratio": max(e_hip[k][0] / e_torch[k][0] for k in range(19) if e_torch[k][0] > 0)}
+    print(json.dumps(rec))
+    if os.environ.get("ACTRAIN_ERROR_OUT"):
+        with open(os.environ["ACTRAIN_ERROR_OUT"], "a") as f:
+            f.write(json.dumps(rec) + "\n")
     pad = ar.padding_mask(off, V, F, A, use_mf, nb)
     assert np.all(g[pad].view(np.uint32) == 0)
     for k in range(19):
@@ -195,6 +212,24 @@ def test_loss_head_with_an_advantage_column(use_mf):
     g_back = tr.grads(cols, n)[0].cpu().numpy()
     g_fresh = handle(case, seed, chunk_rows=chunk).grads(dev_rows(rows), n)[0].cpu().numpy()
     assert same_bits(g_back, g_fresh) and not same_bits(g_back, g)
+
+
+@pytest.mark.parametrize("use_mf", [False, True], ids=["ac", "mfac"])
+def test_loss_head_with_an_advantage_column(use_mf):
+    """ACTrainHIP.grads with an adv column at the Battle shape: 300 rows at chunk_rows = 128 -- three chunks, the last
+    ragged (44 rows), so the column is read at each chunk's row offset and the stats add up over the workgroups of
+    several k_at_loss launches; 300 rows are more than one workgroup's 256.  The checks are _loss_head's."""
+    import actrain_ref as ar
+    _loss_head(tuple(ar.BATTLE) + (use_mf,), 11, 300, 128)
+
+
+@pytest.mark.parametrize("case", [(47, 37, 2, True), (4096, 256, 20, False)], ids=["47-37-2-mf", "4096-256-20"])
+def test_loss_head_with_an_advantage_column_off_the_battle_shape(case):
+    """The same at two of test_actrain_gpu.OFF_SHAPE's shapes, 20 rows (one chunk): two actions under a mean-field value
+    head with h_emb in registers; the widest view and feature rows without one."""
+    from test_actrain_gpu import OFF_SHAPE
+    assert case in OFF_SHAPE
+    _loss_head(case, 11, 20, None)
 
 
 # ------------------------------------------------------------------------------------------------- end to end

@@ -185,3 +185,30 @@ def test_qtrain_preconditions(case):
     assert abs(loss - t_loss) <= 1e-10 * max(1.0, abs(t_loss)) and abs(qa - t_qa) <= 1e-10 * max(1.0, abs(t_qa))
     pad = qr.padding_mask(off, F, A, mf, n)
     assert pad.any() and np.all(g[pad] == 0.0)
+
+
+@pytest.mark.parametrize("T", ns.QTRAIN_SOFT_T)
+@pytest.mark.parametrize("case", ns.QTRAIN_CASES, ids=ns.case_id)
+def test_qtrain_boltzmann_preconditions(case, T):
+    """The case seeds were chosen for the max target.  Under the Boltzmann target (set_target("boltzmann", T)) they
+    must meet that rule's own preconditions: qtarget_ref.check(A, T) passes, no next row of the index list has a
+    non-finite Q value in either net, the float64 target is finite, and every non-empty block's max |g64| under that
+    target is at least 1e-3 (the scale tests/test_net_shapes_gpu.py asserts before it reads a ratio)."""
+    from mfrl_amd.policy import blob_layout
+    F, A, mf, seed = case
+    n, off = blob_layout(F, A, mf)
+    ev, tg = qr.nets(mf, seed, F, A)
+    eb, tb = (qb.packed(m, mf, F, A)[0].astype(np.float64) for m in (ev, tg))
+    ring, idx = qr.ring(seed, F, A), qr.index_list(seed, ns.QTRAIN_B)
+    N = qr.N_RING
+    y, q_e, q_t = ns.qtrain_soft_target64(eb, tb, off, F, A, mf, ring, N, idx, GAMMA, T)
+    assert np.isfinite(q_e).all() and np.isfinite(q_t).all() and np.isfinite(y).all()
+    y_max, _ = qr.targets(eb, tb, off, F, A, mf, ring, N, idx, GAMMA)
+    # another target than the max rule's, by more than f32 resolves ((1, 2) at T = 0.1, gap 0.49: 1.4e-4 at most)
+    assert np.abs(y - y_max).max() > 1e-5
+    g, loss, qa = qr.gradient(eb, tb, off, F, A, mf, ring, N, idx, GAMMA, y=y)
+    for k, (err, scale) in enumerate(qr.block_errors(g, g, off, n)):
+        if not mf and 8 <= k < 12:
+            assert scale == 0.0, k
+            continue
+        assert scale >= 1e-3, (k, scale)

@@ -12,7 +12,8 @@ What the shapes reach that the Battle shape never ran:
   from the start); V < 48 (the 3-slot ring never wraps); V = 4096; A = 32 (no padded policy column), A = 2,
   Ap != A at A = 21 and elsewhere; the plain (kMF = false) instantiation on a mean-field net (value not asked for).
 * The Q network, f32 and bf16: Fp % 16 != 0, F = 1, F = 256 (the bf16 head's eight-step unroll), A = 1, 2, 32.
-* The training step: backward through padded Fp / Ap rows at three more (F, A) pairs, padding staying zero.
+* The training step: backward through padded Fp / Ap rows at three more (F, A) pairs, padding staying zero -- under the
+  max target and under the opt-in Boltzmann target (qt_row<kSoft>) at T = 1 and 0.1.
 
 Bounds: the project's own for a correct kernel -- policy 1e-5, value 1e-5 max(1, max |value|), q 1e-5 max(1, max |q|)
 (the torch f32 modules differ from the float64 network on the same weights by at most 1.8e-6, 4e-7 and 9e-7 of those
@@ -271,3 +272,65 @@ def test_qtrain_padding_stays_zero(case):
         s = tr.get_state(k).cpu().numpy()
         assert np.all(s[c.pad].view(np.uint32) == 0), k
         assert np.any(s[~c.pad] != 0), k
+
+
+def _torch_soft_target(c, idx, T):
+    """torch's own f32 Boltzmann target on the GPU from its own f32 forwards of the next rows
+    (tests/test_qtarget_gpu.py's yardstick)."""
+    nxt = (np.asarray(idx) + 1) % qr.N_RING
+    t = lambda x: torch.as_tensor(np.asarray(x), device="cuda").float()
+    with torch.no_grad():
+        args = (t(c.ring["obs"][nxt]), t(c.ring["feat"][nxt]), t(c.ring["prob"][nxt]) if c.use_mf else None)
+        q_e = copy.deepcopy(c.eval_net).cuda()(*args)
+        q_t = copy.deepcopy(c.target_net).cuda()(*args)
+        v = (torch.softmax(q_e / T, dim=1) * q_t).sum(dim=1)
+        y = t(c.ring["rew"][idx]) + ((1.0 - t(c.ring["term"][idx])) * v) * GAMMA
+    return y.cpu().numpy()
+
+
+@pytest.mark.parametrize("T", ns.QTRAIN_SOFT_T)
+@pytest.mark.parametrize("case", ns.QTRAIN_CASES, ids=ns.case_id)
+def test_qtrain_boltzmann_gradient_accuracy(case, T):
+    """test_qtrain_gradient_accuracy under set_target("boltzmann", T) -- qt_row<kSoft>, tested at the Battle shape alone
+    by tests/test_qtarget_gpu.py::test_gradient_accuracy, whose method this is: the float64 restatement is fed the
+    float64 Boltzmann target (qtarget_ref.target64), the yardstick is torch's f32 autograd with its own f32 Boltzmann
+    target from its own forwards, so both sides carry the target's f32 error.  The checks and the bound are unchanged:
+    per block e_hip <= 4 e_torch on a block scale of at least 1e-3, the padding bits zero, the stats within 1e-4.
+    tests/test_net_shapes_cpu.py::test_qtrain_boltzmann_preconditions holds the case seeds to this rule's own
+    preconditions.  QTRAIN_ERROR_OUT=<path>: the figures are appended there
+    (profiles/qtrain_boltzmann_shapes_error.jsonl is such a run)."""
+    F, A, use_mf, seed = case
+    c = _ctx(case)
+    NR, B = qr.N_RING, ns.QTRAIN_B
+    idx = qr.index_list(seed, B)
+    assert (NR - 1) in idx and len(set(idx.tolist())) < B and c.ring["mask"][idx].sum() >= 15
+    e64, t64 = c.eb.astype(np.float64), c.tb.astype(np.float64)
+    y, q_e, q_t = ns.qtrain_soft_target64(e64, t64, c.off, F, A, use_mf, c.ring, NR, idx, GAMMA, T)
+    assert np.isfinite(q_e).all() and np.isfinite(q_t).all()
+    g64, loss64, qa64 = qr.gradient(e64, t64, c.off, F, A, use_mf, c.ring, NR, idx, GAMMA, y=y)
+    tr = c.handle()
+    tr.set_target("boltzmann", T)
+    g, stats = tr.grads(c.cols, NR, torch.as_tensor(idx, device="cuda"))
+    tr.check_error()
+    g, stats = g.cpu().numpy(), stats.cpu().numpy()
+    named, t_loss, t_qa = qr.torch_gradient(c.eval_net, use_mf, c.ring, idx, _torch_soft_target(c, idx, T), torch.float32,
+                                            "cuda")
+    g_t = qr.pack64(named, F, A, use_mf, c.off, c.n)
+    e_hip, e_torch = qr.block_errors(g, g64, c.off, c.n), qr.block_errors(g_t, g64, c.off, c.n)
+    rec = {"target": "boltzmann", "T": T, "F": F, "A": A, "use_mf": int(use_mf), "seed": seed, "B": B,
+           "e_hip": [e[0] for e in e_hip], "e_torch": [e[0] for e in e_torch], "max_g64": [e[1] for e in e_hip],
+           "loss": float(stats[0]), "loss64": loss64, "torch_loss": t_loss, "mean_qa": float(stats[1]), "mean_qa64": qa64,
+           "max_ratio": max(e_hip[k][0] / e_torch[k][0] for k in range(18) if e_torch[k][0] > 0)}
+    print(json.dumps(rec))
+    if os.environ.get("QTRAIN_ERROR_OUT"):
+        with open(os.environ["QTRAIN_ERROR_OUT"], "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    assert c.pad.any() and np.all(g[c.pad].view(np.uint32) == 0)
+    for k in range(18):
+        if not use_mf and 8 <= k < 12:
+            assert e_hip[k] == (0.0, 0.0), k
+            continue
+        assert e_hip[k][1] >= 1e-3, (k, e_hip[k])
+        assert e_hip[k][0] <= 4.0 * e_torch[k][0], (k, e_hip[k][0], e_torch[k][0])
+    assert abs(float(stats[0]) - loss64) <= 1e-4 * max(1.0, loss64)
+    assert abs(float(stats[1]) - qa64) <= 1e-4 * max(1.0, abs(qa64))

@@ -133,3 +133,19 @@ def test_battle_eval_refuses(argv, msg, capsys):
         battle_eval.main(argv)
     assert ex.value.code == 2
     assert msg in capsys.readouterr().err
+
+
+# ------------------------------------------------------------------------------------------------- the off-shape cases
+def test_shape_cases_are_decisive():
+    """The precondition of tests/test_qsample_shapes_gpu.py, from the references alone: at each case's temperature at
+    least MIN_ROWS of the 131 reference rows do not draw the argmax, and at A = 32 at least MIN_ROWS draw an action
+    >= 24 (the lanes A = 21 leaves empty); the temperature is the first of the list that gives both."""
+    import qsample_cases as qc
+    assert len(qc.CASES) == 18 and {c[:2] for c in qc.CASES} == set(qc.FA)
+    for case in qc.CASES:
+        T = qc.temperature(case)
+        off, high = qc.decisive(case, T)
+        print("%s: T %g, %d rows off the argmax, %d rows >= %d" % (qc.case_id(case), T, off, high, qc.HIGH))
+        assert off >= qc.MIN_ROWS, (case, off)
+        assert case[1] <= qc.HIGH or high >= qc.MIN_ROWS, (case, high)
+        assert np.isfinite(qc.reference_q(case)).all()

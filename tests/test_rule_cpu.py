@@ -8,6 +8,7 @@ import pytest
 
 import acnet_ref
 import common
+import rule_cases as rc
 import rule_ref as rr
 
 MAP, CENTRE, STAY = 40, (20, 20), 6            # STAY: the move (0, 0) of a speed-2 type
@@ -331,3 +332,61 @@ def test_train_battle_refuses(argv, capsys):
         train_battle.main(argv)
     assert ex.value.code == 2
     assert "--eval_" in capsys.readouterr().err
+
+
+# ------------------------------------------------------------------------------------------------- the off-square shapes
+# Preconditions of tests/test_rule_shapes_gpu.py and tests/test_rowmap_gpu.py: properties of the restatement on the
+# shared rows (tests/rule_cases.py), so that a kernel that is wrong off the square view cannot pass there unseen.
+def _transposed(view, v2a):
+    """The same floats read as a (VW, VH) view, with the attack table transposed: what a kernel that takes VH for VW
+    everywhere makes of the row."""
+    n, VH, VW = view.shape[:3]
+    return view.reshape(n, VW, VH, 7), np.ascontiguousarray(v2a.T)
+
+
+@pytest.mark.parametrize("shape", rc.SHAPES)
+def test_shape_rows_take_every_branch(shape):
+    """On each shape's 1000 rows (eps 0.2) every branch tag occurs, at least one best move is refused, moves and
+    attacks both occur; and the restatement on the transposed view differs on at least 10 % of the rows (a floor for
+    the inputs: a shape that misses it gets another seed in rule_cases.SHAPE_SEED, never a lower floor)."""
+    tab = rc.tables(*shape)
+    v2a, base, n_action, move = tab
+    view, feat = rc.shape_rows(shape)
+    want, tag, refused = rc.restated(shape, view, feat, tab)
+    counts = np.bincount(tag, minlength=5)
+    print("%s: tags %s, refused %d" % (shape, dict(zip(rr.TAG_NAMES, counts.tolist())), int(refused.sum())))
+    assert (counts >= 1).all() and refused.sum() >= 1
+    assert 0 <= want.min() and want.max() < n_action and len(np.unique(want)) > base
+    tv, tv2a = _transposed(view, v2a)
+    other = rr.rule_actions(tv, feat, tv2a, base, n_action, move, rc.EPS, rc.SEED, 1000, 0)[0]
+    differ = float((other != want).mean())
+    print("%s: the transposed view changes %.1f %% of the rows" % (shape, 100 * differ))
+    assert differ >= 0.10, differ
+
+
+@pytest.mark.parametrize("name", sorted(rc.HAND_MADE))
+def test_hand_made_tables_reach_the_ranges_ends(name):
+    """(4, 64) with 64 moves and (16, 16) with 57 actions: more than attack_base / 2 distinct actions occur, the rule
+    itself (not the random draw) chooses a move of more than 2 cells on at least one row, the draw reaches the last
+    action, and the tables are what mfx_rule_create accepts (a host call)."""
+    from mfrl_amd.policy import RuleHIP
+    shape, F, tab, (view, feat) = rc.hand_made(name)
+    v2a, base, n_action, move = tab
+    assert feat.shape[1] == F and view.shape[1:3] == shape
+    RuleHIP(shape + (7,), (F,), n_action, base, v2a, move)
+    want, tag, refused = rc.restated(name, view, feat, tab)
+    ruled = want[(tag != rr.TAG_RANDOM) & (want < base)]
+    far = np.abs(move[ruled]).max(axis=1) > 2
+    print("%s: %d distinct actions of %d, %d rule moves past 2 cells, refused %d" % (name, len(np.unique(want)), n_action,
+                                                                                   int(far.sum()), int(refused.sum())))
+    assert len(np.unique(want)) > base / 2
+    assert far.any()
+    assert want.max() == n_action - 1 and (want[tag == rr.TAG_RANDOM] == n_action - 1).any()
+    cy, cx = shape[0] // 2, shape[1] // 2
+    inside = (0 <= cy + move[:, 1]) & (cy + move[:, 1] < shape[0]) & (0 <= cx + move[:, 0]) & (cx + move[:, 0] < shape[1])
+    if name == "strip":
+        assert base == n_action == 64 and (v2a < 0).all() and F == 2 and inside.all()
+        have = {tuple(m) for m in move.tolist()}
+        assert {(0, 0), (16, 0), (-16, 0), (8, 1), (8, -1), (-8, 1), (-8, -1)} <= have
+    else:
+        assert (base, n_action) == (49, 57) and (v2a >= 0).sum() == 8

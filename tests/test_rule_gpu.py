@@ -12,6 +12,7 @@ import pytest
 
 import battle_driver as bd
 import common
+import rule_cases as rc
 import rule_ref as rr
 
 pytestmark = pytest.mark.gpu
@@ -25,65 +26,7 @@ def _cuda(x):
 
 
 # ------------------------------------------------------------------------------------------------- 1: the compact form
-def _tables(VH, VW):
-    """Synthetic tables of a VH x VW view: the 8 cells around the centre attack, the moves of speed 2 (speed 1 in the
-    5 x 5 view, whose 13-move circle would leave the view)."""
-    move = rr.circle_moves(1 if min(VH, VW) < 7 else 2)
-    v2a = np.full((VH, VW), -1, dtype=np.int32)
-    k = 0
-    for r in range(VH // 2 - 1, VH // 2 + 2):
-        for c in range(VW // 2 - 1, VW // 2 + 2):
-            if (r, c) != (VH // 2, VW // 2):
-                v2a[r, c] = k
-                k += 1
-    return v2a, len(move), len(move) + 8, move
-
-
-_ROWS = {}
-
-
-def _synthetic(VH, VW, n=1000, seed=0):
-    """n rows of a VH x VW x 7 view and 12 features, five kinds in turn so that every branch is taken: a sparse enemy
-    fill (A or B), one far enemy among walls and own agents (B, moves refused), no enemy and a minimap with the own
-    bin marked (C-minimap, moves refused), no enemy and an empty minimap (C-centre; x / W and y / H on either side
-    of and exactly at 0.5), and every channel filled at random; a third of the minimap rows carry exactly 1.0 at the
-    own bin, i.e. no own bin (> 1.0), which sends them to the centre.  Made once per shape, never modified."""
-    key = (VH, VW, n, seed)
-    if key in _ROWS:
-        return _ROWS[key]
-    rng = np.random.RandomState(1000 * VH + VW + seed)
-    view = np.zeros((n, VH, VW, 7), dtype=np.float32)
-    feat = rng.uniform(0, 1, size=(n, 12)).astype(np.float32)
-    feat[:, -2:] = rng.choice(np.array([0.25, 0.5, 0.75], dtype=np.float32), size=(n, 2))
-    for i in range(n):
-        kind, v = i % 5, view[i]
-        v[VH // 2, VW // 2, rr.CH_OWN] = 1
-        if kind == 0:
-            v[:, :, rr.CH_ENEMY] = rng.uniform(size=(VH, VW)) < 0.04
-            v[VH // 2, VW // 2, rr.CH_ENEMY] = 0
-        elif kind == 1:
-            edge = [(r, c) for r in range(VH) for c in range(VW) if r in (0, VH - 1) or c in (0, VW - 1)]
-            r, c = edge[rng.randint(len(edge))]
-            v[r, c, rr.CH_ENEMY] = 1
-            v[:, :, rr.CH_WALL] = rng.uniform(size=(VH, VW)) < 0.3
-            v[:, :, rr.CH_OWN] = rng.uniform(size=(VH, VW)) < 0.3
-            v[r, c, rr.CH_WALL] = v[r, c, rr.CH_OWN] = 0
-        elif kind in (2, 3):
-            own = rng.randint(VH), rng.randint(VW)
-            v[:, :, rr.CH_OWN_MM] = (rng.uniform(size=(VH, VW)) < 0.1) * np.float32(0.125)
-            v[own[0], own[1], rr.CH_OWN_MM] += 1
-            if i % 3:                                            # (else often exactly 1.0: a row without an own bin)
-                v[own[0], own[1], rr.CH_OWN_MM] = np.float32(1.125)
-            if kind == 2:
-                v[:, :, rr.CH_ENEMY_MM] = rng.randint(0, 4, size=(VH, VW)) * (rng.uniform(size=(VH, VW)) < 0.2) * np.float32(0.0625)
-                v[:, :, rr.CH_WALL] = rng.uniform(size=(VH, VW)) < 0.3
-            elif i % 2:
-                v[:, :, rr.CH_ENEMY_MM] = np.float32(0.25) * (rng.uniform() < 0.5)      # (flat: only the own bin's + 1 stands out)
-            v[own[0], own[1], rr.CH_ENEMY_MM] += 1
-        else:
-            view[i] = (rng.uniform(size=(VH, VW, 7)) < 0.15) * rng.choice(np.array([0.5, 1.0, 2.0], np.float32), size=(VH, VW, 7))
-    _ROWS[key] = (view, feat)
-    return _ROWS[key]
+_tables, _synthetic = rc.tables, rc.synthetic          # (shared with tests/test_rule_shapes_gpu.py)
 
 
 @pytest.mark.parametrize("shape", [(5, 5), (13, 13), (15, 15)])

@@ -2,7 +2,11 @@
 general reward DSL (RewardEngine.cc:216-443: attack / kill / collide / at / in / die / in_a_line,
 and / or / not, 'any' / 'all' / fixed-index symbols, group receivers, terminal rules) on the HIP
 engine, step for step against the reference build (oracle/_ref) on the same seeded scenario:
-views, features, rewards, alive flags, positions, ids and done after every step."""
+views, features, rewards, alive flags, positions, ids and done after every step.
+
+At the end: mfx_battle_view_support against the observations of these games (and of the generic rollout config, per
+call and on the rollout's view buffer) -- every view row is zero outside the mask.  tests/test_abi_cpu.py repeats it on
+the reference build's observations without a GPU."""
 import os
 
 import numpy as np
@@ -140,9 +144,7 @@ def test_pursuit_matches_reference(seed):
     assert any(np.any(r[4] > 0.5) for r in ref), "no predator hit a prey: the test is vacuous"
 
 
-def test_odd_bodies_fill_and_custom_placement():
-    """2x3 and 3x1 bodies placed by 'fill' (body-size strides) and 'custom' (overlaps skipped), with
-    minimap mode, starvation removing whole bodies and a kill-triggered rule."""
+def _odd_config():
     import magent
     gw = magent.gridworld
     cfg = gw.Config()
@@ -155,35 +157,42 @@ def test_odd_bodies_fill_and_custom_placement():
     g0, g1 = cfg.add_group(big), cfg.add_group(long_)
     a, b = gw.AgentSymbol(g0, "any"), gw.AgentSymbol(g1, "any")
     cfg.add_reward_rule(gw.Event(a, "kill", b) | gw.Event(b, "kill", a), receiver=[a, b], value=[1.0, 1.0])
+    return cfg
 
-    def run(lib_path):
-        env, (h0, h1) = common.config_env(lib_path, cfg, 18)
-        env.set_seed(9)
-        rs = np.random.RandomState(9)
-        env.reset()
-        env.add_agents(h0, method="fill", pos=[2, 2], size=[7, 9])
-        env.add_agents(h1, method="custom", pos=[[10, 3], [11, 3], [10, 5], [12, 8], [3, 3], [14, 12], [9, 14]])
-        env.add_agents(h1, method="fill", pos=[10, 10], size=[6, 3])
-        out = []
-        for t in range(40):
-            rec = []
-            for h in (h0, h1):
-                view, feat = env.get_observation(h)
-                rec += [view.copy(), feat.copy()]
-            for h in (h0, h1):
-                env.set_action(h, rs.randint(0, env.get_action_space(h)[0], env.get_num(h)).astype(np.int32))
-            done = env.step()
-            for h in (h0, h1):
-                rec += [env.get_reward(h).copy(), env.get_alive(h).copy(), env.get_pos(h).copy()]
-            rec.append(np.array([done]))
-            out.append(rec)
-            env.clear_dead()
-            if done:
-                break
-        del env
-        return out
 
-    _compare(run(common.HIP_LIB), run(common.REF_LIB))
+def _odd_run(lib_path, cfg):
+    env, (h0, h1) = common.config_env(lib_path, cfg, 18)
+    env.set_seed(9)
+    rs = np.random.RandomState(9)
+    env.reset()
+    env.add_agents(h0, method="fill", pos=[2, 2], size=[7, 9])
+    env.add_agents(h1, method="custom", pos=[[10, 3], [11, 3], [10, 5], [12, 8], [3, 3], [14, 12], [9, 14]])
+    env.add_agents(h1, method="fill", pos=[10, 10], size=[6, 3])
+    out = []
+    for t in range(40):
+        rec = []
+        for h in (h0, h1):
+            view, feat = env.get_observation(h)
+            rec += [view.copy(), feat.copy()]
+        for h in (h0, h1):
+            env.set_action(h, rs.randint(0, env.get_action_space(h)[0], env.get_num(h)).astype(np.int32))
+        done = env.step()
+        for h in (h0, h1):
+            rec += [env.get_reward(h).copy(), env.get_alive(h).copy(), env.get_pos(h).copy()]
+        rec.append(np.array([done]))
+        out.append(rec)
+        env.clear_dead()
+        if done:
+            break
+    del env
+    return out
+
+
+def test_odd_bodies_fill_and_custom_placement():
+    """2x3 and 3x1 bodies placed by 'fill' (body-size strides) and 'custom' (overlaps skipped), with
+    minimap mode, starvation removing whole bodies and a kill-triggered rule."""
+    cfg = _odd_config()
+    _compare(_odd_run(common.HIP_LIB, cfg), _odd_run(common.REF_LIB, cfg))
 
 
 def _mode_config(map_size, turn, food, minimap, goal=False, big=False):
@@ -206,9 +215,11 @@ def _mode_config(map_size, turn, food, minimap, goal=False, big=False):
     return cfg
 
 
-@pytest.mark.parametrize("turn,food,minimap,big,seed", [
-    (True, False, False, False, 11), (True, False, True, True, 12), (False, True, True, False, 13),
-    (False, True, False, True, 14), (True, True, True, False, 15), (True, True, False, True, 16)])
+MODE_GRID = [(True, False, False, False, 11), (True, False, True, True, 12), (False, True, True, False, 13),
+             (False, True, False, True, 14), (True, True, True, False, 15), (True, True, False, True, 16)]
+
+
+@pytest.mark.parametrize("turn,food,minimap,big,seed", MODE_GRID)
 def test_turn_and_food_modes_match_reference(turn, food, minimap, big, seed):
     """turn_mode (random directions from the LCG, turn actions with the reference's wise = 2a - 1,
     direction-relative moves / attacks / views, bodies pivoting about their real corner) and
@@ -260,3 +271,110 @@ def test_kill_supply_over_64_attackers_matches_reference():
     """builtin/config/forest.py crowded: ~90 tiger attacks a step, past the wave form -- with kill_supply the attack
     walks the serial order there while the moves keep the parallel forms (par_step stays on)."""
     _both("forest", 24, (60, 150), 5, steps=30, walls=6)
+
+
+# ------------------------------------------------------------------------------------------------- view_support
+# mfx_battle_view_support promises that group g's observation is zero outside the mask; ACNetHIP.set_input_support and
+# ActorCritic's HIP training rely on it for bit-identity, whatever the config.  The games above, replayed on the engine
+# under test: name -> (config, map size, play(lib) -> records whose entries 0, 2, ... are the groups' views).
+def _generic_config(map_size):
+    from test_rollout_gpu import _generic_config as make
+    return make(map_size)
+
+
+def support_games():
+    games = {"forest": ("forest", 20, lambda lib: _play(lib, "forest", 20, (40, 30), 1, 40, 10)),
+             "double_attack": ("double_attack", 14, lambda lib: _play(lib, "double_attack", 14, (30, 60), 1, 60, 10)),
+             "pursuit": ("pursuit", 20, lambda lib: _play(lib, "pursuit", 20, (12, 40), 1, 60, 10))}
+    for turn, food, minimap, big, seed in MODE_GRID:
+        cfg = _mode_config(16, turn, food, minimap, big=big)
+        name = "turn%d-food%d-minimap%d-big%d" % (turn, food, minimap, big)
+        games[name] = (cfg, 16, lambda lib, cfg=cfg, seed=seed: _play(lib, cfg, 16, (14, 30), seed, 60, 6))
+    odd = _odd_config()
+    games["odd_bodies"] = (odd, 18, lambda lib: _odd_run(lib, odd))
+    gen = _generic_config(32)
+    games["generic"] = (gen, 32, lambda lib: _play(lib, gen, 32, (40, 40), 3, 40, 10))
+    return games
+
+
+SUPPORT_GAMES = ["forest", "double_attack", "pursuit", "turn1-food0-minimap0-big0", "turn1-food0-minimap1-big1",
+                 "turn0-food1-minimap1-big0", "turn0-food1-minimap0-big1", "turn1-food1-minimap1-big0",
+                 "turn1-food1-minimap0-big1", "odd_bodies", "generic"]
+
+
+def support_masks(config, map_size):
+    """[(mask bool [view_h, view_w, n_ch], the group's view range is a circle)] per group, from
+    mfx_battle_view_support of a drop-in env of the config (host work only: the parameters compile without a GPU)."""
+    import ctypes
+    env, handles = common.config_env(common.HIP_LIB, config, map_size)
+    dll = env._lib.dll
+    dll.mfx_battle_view_support.restype = ctypes.c_int
+    out = []
+    for g, h in enumerate(handles):
+        shape = tuple(int(x) for x in env.get_view_space(h))
+        m = np.full(int(np.prod(shape)), 2, dtype=np.uint8)
+        assert dll.mfx_battle_view_support(env.game, g, m.ctypes.data_as(ctypes.c_void_p), m.size) == 0
+        assert set(np.unique(m).tolist()) <= {0, 1}
+        rng = env._config.agent_type_dict[env._config.groups[g]]["view_range"]
+        out.append((m.reshape(shape).astype(bool), type(rng).__name__ == "CircleRange"))
+    return out
+
+
+def check_support(name, records, masks):
+    """Every view row of every recorded step is exactly zero outside its group's mask; a circular view range leaves
+    some input outside; the views are not zero inside (the check is not vacuous).  -> rows checked."""
+    rows = 0
+    for g, (mask, circle) in enumerate(masks):
+        if circle:
+            assert not mask.all(), (name, g)
+        inside = False
+        for t, rec in enumerate(records):
+            view = rec[2 * g]
+            assert view.shape[1:] == mask.shape, (name, g, view.shape, mask.shape)
+            bad = (view != 0) & ~mask
+            assert not bad.any(), (name, "group %d step %d" % (g, t), np.argwhere(bad)[:5].tolist())
+            inside = inside or bool((view != 0)[:, mask].any())
+            rows += len(view)
+        assert inside, (name, g)
+    return rows
+
+
+@pytest.mark.parametrize("name", SUPPORT_GAMES)
+def test_view_support_covers_the_observation(name):
+    """The drop-in env's observations of the games above, step by step, against mfx_battle_view_support."""
+    config, map_size, play = support_games()[name]
+    rows = check_support(name, play(common.HIP_LIB), support_masks(config, map_size))
+    assert rows > 100
+
+
+def test_view_support_covers_the_rollout_view_buffer():
+    """The generic config (11 x 11 view, no minimap) on the device rollout loop: the live rows of the view buffers,
+    after each of 30 steps, against BattleBatch.view_support -- the mask ACNetHIP.act_rollout(support=True) and
+    ActorCritic's HIP training take."""
+    import torch
+    import battle_driver as bd
+    from mfrl_amd.battle import BattleBatch
+    map_size, E = 32, 2
+    cfg = _generic_config(map_size)
+    left, right = bd.block_positions(map_size, 40)
+    eng = BattleBatch(map_size, E, config=cfg, stream=torch.cuda.current_stream())
+    eng.rollout_init([left, right], max_steps=20, eps=0.3, seed=99, stagger=False)
+    rc = eng.rowcap
+    masks = [eng.view_support(g).astype(bool) for g in range(2)]
+    for (m, _), mine in zip(support_masks(cfg, map_size), masks):
+        assert np.array_equal(m.reshape(-1), mine) and not mine.all()
+    rows = 0
+    for t in range(30):
+        eng.rollout_step(1)
+        num = torch.empty((E, 2), dtype=torch.int32)
+        eng.rollout_copy("group_num", num)
+        for g in range(2):
+            view = torch.empty((E, rc, masks[g].size), dtype=torch.float32)
+            eng.rollout_copy("view", view, group=g)
+            eng.sync()
+            for e in range(E):
+                live = view[e, :min(int(num[e, g]), rc)].numpy()
+                assert not live[:, ~masks[g]].any(), (t, e, g)
+                assert live[:, masks[g]].any()
+                rows += len(live)
+    assert rows > 1000
