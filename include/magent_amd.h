@@ -816,6 +816,25 @@ int mfx_qtrain_error(void *handle, int *code, long long *bad_value, void *stream
  *                    DESIGN 7q) where the default forms ret - v; the value term and dL/dv use ret - v either way, ret
  *                    being the reward column after the walk.  The column must stay valid until those calls have run.
  *                    Null restores the default, bit for bit a fresh handle's.  mfx_actrain_rows is unchanged.
+ *   set_ppo          d_logp_old: a float32 column of n rows, or null (the default).  Host state, read by the grads / step
+ *                    calls that follow (opt-in; tests/ppo_ref.py restates it): with a column the policy term
+ *                    is PPO's clipped surrogate.  Per row, in f32 with no contraction, lp = log(p_a + 1e-6f) as above and
+ *                    adv = the advantage column's entry:
+ *                        d = lp - d_logp_old[i];  r = expf(d);  lo = (float)(1.0 - clip);  hi = (float)(1.0 + clip)
+ *                        clipped = (adv > 0 && r > hi) || (adv < 0 && r < lo)     (strict: a row on the bound is not)
+ *                        dL/dp_a gets -(adv r) / (p_a + 1e-6) / n where the default adds -adv / (p_a + 1e-6) / n, and
+ *                                nothing when clipped;  the row's policy loss is -adv r, clipped: -adv (adv > 0 ? hi : lo)
+ *                    The value term, dL/dv, the entropy term, the clamp's mask, the / n, the action check and the error
+ *                    word are the default's; d_stats stays four floats (pg_loss the mean of the row terms above).  Two
+ *                    more means over the call's n rows -- clip_frac, of clipped ? 1 : 0, and approx_kl, of (r - 1) - d
+ *                    (the non-negative k3 estimate) -- are summed like the stats (per-workgroup partials in index order,
+ *                    in double) into two device floats the handle owns.  d_logp_new (may be null): lp is stored there per
+ *                    row.  clip must be finite and > 0 (NaN is refused), before any launch; a grads / step call with
+ *                    d_logp_old set and no advantage column is refused.  The columns must stay valid until those calls
+ *                    have run.  Null d_logp_old restores the default, bit for bit a fresh handle's (clip and d_logp_new
+ *                    are not read).
+ *   ppo_stats        a device-to-device copy on `stream` of (clip_frac, approx_kl) of the last grads / step call made
+ *                    with d_logp_old set, into d_out2 [2]; (0, 0) before any such call.  Nothing synchronises.
  *   grads           the gradient in blob layout (padding exactly zero) into d_grad_blob and (pg_loss, vf_loss, ent_loss,
  *                    mean value) -- vf_loss and ent_loss with their coefficients, as ActorCritic.train prints them -- into
  *                    d_stats (either may be null); no state changes; bit for bit the gradient step applies
@@ -848,10 +867,20 @@ int mfx_actrain_step_count(void *handle, long long *t);
 int mfx_actrain_set_input_support(void *handle, const uint8_t *mask, int n, void *stream);
 int mfx_actrain_set_chunk_rows(void *handle, int chunk_rows);
 int mfx_actrain_set_advantage(void *handle, const float *d_adv);
+int mfx_actrain_set_ppo(void *handle, const float *d_logp_old, double clip, float *d_logp_new);
+int mfx_actrain_ppo_stats(void *handle, float *d_out2, void *stream);
 int mfx_actrain_grads(void *handle, const mfx_actrain_rows *rows, long long n, float *d_grad_blob, float *d_stats,
                       void *stream);
 int mfx_actrain_step(void *handle, const mfx_actrain_rows *rows, long long n, float *d_stats, void *stream);
 int mfx_actrain_error(void *handle, int *code, long long *bad_value, void *stream);
+
+/* The behaviour log-probabilities of the PPO head (csrc/ppo_kernels.hip; opt-in): d_logp[i] = logf(d_policy[i
+ * n_action + a] + 1e-6f) with a = d_act[i], for i < n.  d_policy: [n][n_action], the clamped policy mfx_acnet_forward
+ * writes.  The action is checked before it selects anything: a row whose action is outside [0, n_action) reads nothing
+ * from the policy and gets +0; the training step that follows on those rows reports it (MFX_ACTRAIN_BAD_ACTION) and
+ * applies nothing.  n = 0 does nothing; n_action outside 2..32 is refused.  One lane per row: no atomics, nothing is
+ * read back, equal input gives bitwise equal output. */
+int mfx_policy_logp(const float *d_policy, const int32_t *d_act, long long n, int n_action, float *d_logp, void *stream);
 
 /* ---------------------------------------------------------------- measurement */
 /* The HBM write ceiling on this device, measured in-process beside the bench (csrc/diag_kernels.hip): total_bytes

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -254,6 +255,84 @@ __global__ void __launch_bounds__(256) k_at_loss(LossArgs a, const float* __rest
     if (tid < 4) a.part[(size_t)blockIdx.x * 4 + tid] = red[tid][0];
 }
 
+// The PPO head (mfx_actrain_set_ppo): the ADV = true head with the policy term replaced by the clipped
+// surrogate of the probability ratio r = exp(lp_a - lp_old[i]).  A row is clipped when its ratio has left [lo, hi] in
+// the direction its advantage pushes (strictly: a row on the bound is not clipped); a clipped row's policy term is the
+// constant -adv bound and adds nothing to dL/dp.  Two more per-row terms go to part2 [workgroups][2]: clipped ? 1 : 0
+// and (r - 1) - d, the k3 estimate of the KL.  lp_new (may be null): lp_a per row.  A sibling of k_at_loss and not a
+// third instantiation of it, so that the two existing heads keep their symbols and their code
+// (profiles/ppo_resources.txt); everything outside the policy term is that kernel's text.
+struct PpoArgs {
+    const float* adv;         // the chunk's rows of the three columns
+    const float* lp_old;
+    float* lp_new;
+    float* part2;             // [workgroups][2]
+    float lo, hi;
+};
+
+__global__ void __launch_bounds__(256) k_at_loss_ppo(LossArgs a, PpoArgs o) {
+    __shared__ float red[6][256];
+    __shared__ float sk[32][256];                        // the row's softmax, one column per thread
+    const int tid = threadIdx.x, i = blockIdx.x * 256 + tid;
+    float st[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (i < a.rows) {
+        int ac = a.act[i];
+        if (ac < 0 || ac >= a.A) {
+            if (atomicCAS(&a.err[0], 0, (int)MFX_ACTRAIN_BAD_ACTION) == 0) { a.err[1] = ac; a.err[2] = ac < 0 ? -1 : 0; }
+            ac = 0;
+        }
+        float* z = a.Z + (size_t)i * 32;
+        const int A = a.A;
+        float mx = -__builtin_huge_valf();
+        for (int k = 0; k < A; ++k) mx = fmaxf(mx, z[k]);
+        float sum = 0.f;
+        for (int k = 0; k < A; ++k) {
+            const float e = expf(z[k] - mx);
+            sk[k][tid] = e;
+            sum += e;
+        }
+        const float v = a.val[i], R = a.ret[i], adv = o.adv[i];
+        // the taken action's log-probability first: the ratio decides what the loop below adds at k == ac
+        const float sa = sk[ac][tid] / sum;
+        const float lpa = logf(fminf(fmaxf(sa, 1e-10f), 1.0f - 1e-10f) + 1e-6f);
+        const float d = lpa - o.lp_old[i];
+        const float r = expf(d);
+        const bool clipped = (adv > 0.f && r > o.hi) || (adv < 0.f && r < o.lo);
+        if (o.lp_new) o.lp_new[i] = lpa;
+        float ent = 0.f, dot = 0.f;
+        for (int k = 0; k < A; ++k) {
+            const float sx = sk[k][tid] / sum;
+            const float p = fminf(fmaxf(sx, 1e-10f), 1.0f - 1e-10f);
+            const float q = p + 1e-6f, lp = logf(q);
+            ent += p * lp;
+            float gk = a.ent_coef * (lp + p / q);
+            if (k == ac && !clipped) gk += -(adv * r) / q;
+            const bool inside = sx >= 1e-10f && sx <= 1.0f - 1e-10f;             // torch's clamp backward
+            gk = inside ? gk / a.n_rows : 0.f;
+            dot += sx * gk;
+            sk[k][tid] = sx;
+            z[k] = gk;
+        }
+        for (int k = 0; k < 32; ++k) z[k] = k < A ? sk[k][tid] * (z[k] - dot) : 0.f;
+        a.dv[i] = (-2.f * a.value_coef * (R - v)) / a.n_rows;
+        st[0] = clipped ? -adv * (adv > 0.f ? o.hi : o.lo) : -adv * r;
+        st[1] = (R - v) * (R - v); st[2] = ent; st[3] = v;
+        st[4] = clipped ? 1.f : 0.f; st[5] = (r - 1.f) - d;
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) red[q][tid] = st[q];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {                  // a fixed tree
+        if (tid < w) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) red[q][tid] += red[q][tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid < 4) a.part[(size_t)blockIdx.x * 4 + tid] = red[tid][0];
+    else if (tid < 6) o.part2[(size_t)blockIdx.x * 2 + (tid - 4)] = red[tid][0];
+}
+
 // stats = (pg, value_coef vf, ent_coef neg_entropy, mean value): the workgroups' partials in order, in double
 __global__ void k_at_stats(const float* __restrict__ part, int nblocks, double inv_n, float value_coef, float ent_coef,
                            float* __restrict__ stats) {
@@ -265,6 +344,15 @@ __global__ void k_at_stats(const float* __restrict__ part, int nblocks, double i
     if (q == 1) s *= (double)value_coef;
     if (q == 2) s *= (double)ent_coef;
     stats[q] = (float)s;
+}
+
+// (clip_frac, approx_kl): the PPO head's two partials per workgroup, in order, in double, over the call's n
+__global__ void k_at_ppo_stats(const float* __restrict__ part2, int nblocks, double inv_n, float* __restrict__ out) {
+    const int q = threadIdx.x;
+    if (q >= 2) return;
+    double s = 0.0;
+    for (int b = 0; b < nblocks; ++b) s += (double)part2[(size_t)b * 2 + q];
+    out[q] = (float)(s * inv_n);
 }
 
 // dD[i][j] = D[i][j] > 0 ? (sum_a dz[i][a] Wp[j][a]) / 0.1 (+ dv[i] wval[j][0], AC) : 0
@@ -379,6 +467,10 @@ struct ACTrain {
     int supK = 0;
     int chunk = kATDefaultChunk;
     const float* adv = nullptr;          // the advantage column of the next grads / step calls (null: ret - v)
+    const float* lp_old = nullptr;       // mfx_actrain_set_ppo: the behaviour log-probabilities (null: no PPO head)
+    float* lp_new = nullptr;
+    float ppo_lo = 0.f, ppo_hi = 0.f;
+    DevBuf<float> pp, pstat;             // the PPO head's partials [workgroups][2]; (clip_frac, approx_kl)
     DevBuf<float> act, part, sp;         // the chunk's activations and intermediates; the K slices' blobs; stats partials
     DevBuf<double> bias;                 // dsum [kATBias], then dpart [slices][kATBias]
     size_t part_slices = 0;
@@ -402,6 +494,9 @@ int at_gemm(hipStream_t st, bool AT, bool BT, bool wide, const GemmArgs& g, int 
 // The gradient of the n rows into the handle's gradient blob, and the stats.
 int at_gradient(ACTrain* h, const mfx_actrain_rows* rows, long long n, float* d_stats, hipStream_t st) {
     if (n < 1) return fail("actrain: %lld rows (at least 1)", n);
+    if (h->lp_old && !h->adv)
+        return fail("actrain: d_logp_old is set (mfx_actrain_set_ppo) without an advantage column "
+                    "(mfx_actrain_set_advantage): the PPO head reads both");
     if (!rows || !rows->obs || !rows->feat || !rows->act || !rows->ret || (h->use_mf && !rows->prob))
         return fail("actrain: a row column is missing");
     const int cmax = (int)std::min<long long>(n, h->chunk);
@@ -412,6 +507,10 @@ int at_gradient(ACTrain* h, const mfx_actrain_rows* rows, long long n, float* d_
     try {
         h->act.ensure(per_row * cmax);
         h->sp.ensure(nblocks * 4);
+        if (h->lp_old) {
+            h->pp.ensure(nblocks * 2);
+            h->pstat.ensure(2);
+        }
         h->bias.ensure((size_t)(1 + smax) * kATBias);
         if ((size_t)smax > h->part_slices) {
             h->part.ensure((size_t)smax * h->blob_n);
@@ -476,7 +575,11 @@ int at_gradient(ACTrain* h, const mfx_actrain_rows* rows, long long n, float* d_
         const int lb = (m + 255) / 256;
         LossArgs la{Z, VAL, rows->act + r0, rows->ret + r0, DV, h->sp.p + block0 * 4, h->err, m, A, n_rows,
                     (float)h->value_coef, (float)h->ent_coef};
-        if (h->adv) k_at_loss<true><<<lb, 256, 0, st>>>(la, h->adv + r0);
+        if (h->lp_old) {
+            const PpoArgs po{h->adv + r0, h->lp_old + r0, h->lp_new ? h->lp_new + r0 : nullptr, h->pp.p + block0 * 2,
+                             h->ppo_lo, h->ppo_hi};
+            k_at_loss_ppo<<<lb, 256, 0, st>>>(la, po);
+        } else if (h->adv) k_at_loss<true><<<lb, 256, 0, st>>>(la, h->adv + r0);
         else k_at_loss<false><<<lb, 256, 0, st>>>(la, nullptr);
         block0 += (size_t)lb;
         // ---- row-side backward (NT): C = mask (A W^T [+ C])
@@ -538,6 +641,7 @@ int at_gradient(ACTrain* h, const mfx_actrain_rows* rows, long long n, float* d_
     k_at_bias_out<<<dim3(2, nj), 256, 0, st>>>(jb, dsum, grad);
     k_at_stats<<<1, 64, 0, st>>>(h->sp.p, (int)block0, 1.0 / (double)n, (float)h->value_coef, (float)h->ent_coef,
                                  d_stats ? d_stats : reinterpret_cast<float*>(h->err + 4));
+    if (h->lp_old) k_at_ppo_stats<<<1, 64, 0, st>>>(h->pp.p, (int)block0, 1.0 / (double)n, h->pstat.p);
     MFX_HIP(hipGetLastError());
     return 0;
 }
@@ -664,6 +768,34 @@ MFX_API int mfx_actrain_set_advantage(void* handle, const float* d_adv) {
     auto* h = static_cast<ACTrain*>(handle);
     if (!h) return fail("actrain: null handle");
     h->adv = d_adv;
+    return 0;
+}
+
+MFX_API int mfx_actrain_set_ppo(void* handle, const float* d_logp_old, double clip, float* d_logp_new) {
+    auto* h = static_cast<ACTrain*>(handle);
+    if (!h) return fail("actrain: null handle");
+    if (!d_logp_old) {
+        h->lp_old = nullptr;
+        h->lp_new = nullptr;
+        return 0;
+    }
+    if (!(clip > 0.0) || !std::isfinite(clip)) return fail("actrain_set_ppo: clip %g must be finite and > 0", clip);
+    h->lp_old = d_logp_old;
+    h->lp_new = d_logp_new;
+    h->ppo_lo = (float)(1.0 - clip);
+    h->ppo_hi = (float)(1.0 + clip);
+    return 0;
+}
+
+MFX_API int mfx_actrain_ppo_stats(void* handle, float* d_out2, void* stream) {
+    auto* h = static_cast<ACTrain*>(handle);
+    if (!h) return fail("actrain: null handle");
+    if (!d_out2) return fail("actrain_ppo_stats: null d_out2");
+    if (!h->pstat.p) {                    // no PPO gradient yet
+        MFX_HIP(hipMemsetAsync(d_out2, 0, 2 * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
+    MFX_HIP(hipMemcpyAsync(d_out2, h->pstat.p, 2 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 

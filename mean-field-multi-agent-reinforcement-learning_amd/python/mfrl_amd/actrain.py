@@ -141,21 +141,51 @@ class ACTrainHIP:
                 adv.shape[0] >= n, "ACTrainHIP: column adv must be a contiguous float32 CUDA vector of at least n rows"
         check(self._L.mfx_actrain_set_advantage(self.handle, ptr(adv)), "mfx_actrain_set_advantage")
 
-    def grads(self, cols, n):
-        """(gradient blob, stats (pg_loss, vf_loss, ent_loss, mean value)) of rows [0, n).  No state changes."""
+    def _set_ppo(self, cols, n, clip):
+        """cols.get("logp_old") with clip: the float32 column of the behaviour log-probabilities (n rows;
+        ActorCritic.objective = "ppo", replay.policy_logp) -- the policy term becomes PPO's clipped surrogate (the
+        contract of mfx_actrain_set_ppo) -- or None for the default.  cols.get("logp_new"): an optional float32 output
+        column, the rows' current log-probabilities.  Set on every call, like the advantage column."""
+        old, new = cols.get("logp_old"), cols.get("logp_new")
+        if old is None:
+            if clip is not None or new is not None:
+                raise ValueError("ACTrainHIP: clip / column logp_new belong to column logp_old: give that too")
+            check(self._L.mfx_actrain_set_ppo(self.handle, None, 0.0, None), "mfx_actrain_set_ppo")
+            return
+        if clip is None:
+            raise ValueError("ACTrainHIP: column logp_old needs clip=")
+        for k, t in (("logp_old", old), ("logp_new", new)):
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 1 and
+                                 t.shape[0] >= n), \
+                "ACTrainHIP: column %s must be a contiguous float32 CUDA vector of at least n rows" % k
+        check(self._L.mfx_actrain_set_ppo(self.handle, ptr(old), float(clip), ptr(new)), "mfx_actrain_set_ppo")
+
+    def ppo_stats(self):
+        """(clip_frac, approx_kl) of the last grads / step call with a logp_old column: a float32 CUDA tensor of 2, copied
+        on the current stream; nothing synchronises."""
+        out = torch.empty(2, dtype=torch.float32, device="cuda")
+        check(self._L.mfx_actrain_ppo_stats(self.handle, ptr(out), stream()), "mfx_actrain_ppo_stats")
+        return out
+
+    def grads(self, cols, n, clip=None):
+        """(gradient blob, stats (pg_loss, vf_loss, ent_loss, mean value)) of rows [0, n).  No state changes.
+        clip: with cols["logp_old"], the PPO head's clip range (_set_ppo)."""
         rows, n = self._rows(cols, n)
         self._set_advantage(cols, n)
+        self._set_ppo(cols, n, clip)
         g = torch.empty(self.blob_n, dtype=torch.float32, device="cuda")
         stats = torch.zeros(4, dtype=torch.float32, device="cuda")
         check(self._L.mfx_actrain_grads(self.handle, ctypes.byref(rows), n, ptr(g), ptr(stats), stream()),
               "mfx_actrain_grads")
         return g, stats
 
-    def step(self, cols, n):
+    def step(self, cols, n, clip=None):
         """One gradient over rows [0, n) and one Adam step; -> the stats on the device.  Nothing synchronises: call
-        check_error() before trusting the result."""
+        check_error() before trusting the result.  clip: as grads'.  A minibatch is rows [a, b) passed as cols[k][a:b]
+        with n = b - a: the columns are read from their first row, no gather is made."""
         rows, n = self._rows(cols, n)
         self._set_advantage(cols, n)
+        self._set_ppo(cols, n, clip)
         stats = torch.zeros(4, dtype=torch.float32, device="cuda")
         check(self._L.mfx_actrain_step(self.handle, ctypes.byref(rows), n, ptr(stats), stream()), "mfx_actrain_step")
         return stats

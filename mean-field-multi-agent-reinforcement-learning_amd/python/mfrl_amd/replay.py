@@ -275,6 +275,27 @@ def adv_normalize(adv):
     return adv
 
 
+def policy_logp(policy, act, out):
+    """out[i] = log(policy[i, act[i]] + 1e-6) in float32 for the n rows of `policy` (HIP kernel k_policy_logp; the
+    contract is mfx_policy_logp's in include/magent_amd.h): policy [n, A] float32 (ACNetHIP.forward's clamped policy),
+    act int32 and out float32 of at least n rows.  A row whose action is outside [0, A) gets +0 -- the training step on
+    those rows reports it.  Nothing is read back.  -> out."""
+    assert policy.is_cuda and policy.dtype == torch.float32 and policy.is_contiguous() and policy.dim() == 2
+    n, A = policy.shape
+    assert act.is_cuda and act.dtype == torch.int32 and act.is_contiguous() and act.dim() == 1 and len(act) >= n
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 1 and len(out) >= n
+    check(lib().mfx_policy_logp(ptr(policy), ptr(act), int(n), int(A), ptr(out), stream()), "mfx_policy_logp")
+    return out
+
+
+def ppo_order(seed, round, epoch, M):
+    """The order in which epoch `epoch` of round `round` takes the M minibatch segments of ActorCritic.objective =
+    "ppo": a permutation of range(M) from a generator of its own, keyed by the three integers -- equal keys give equal
+    orders, and the global np.random stream is not drawn from."""
+    rng = np.random.Generator(np.random.PCG64([int(seed), int(round), int(epoch)]))
+    return [int(k) for k in rng.permutation(int(M))]
+
+
 def chain_links(keys):
     """Host restatement of the linked collector's two columns, for the tests: for the key column of step-major
     rows, prev[r] = the latest earlier row with the same key (or -1) and tail[r] = no later row has it."""

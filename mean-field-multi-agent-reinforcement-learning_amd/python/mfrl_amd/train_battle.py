@@ -11,6 +11,7 @@
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --explore boltzmann --target boltzmann ...   # + the paper's v^MF target
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --mean_field neighbors --mf_radius 6 ...   # the paper's neighbourhood mean action
     python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes --advantage gae --gae_lambda 0.95 --adv_norm ...   # GAE(lambda) advantages, normalised per round
+    python -m mfrl_amd.train_battle --algo mfac --envs 64 --rollout_episodes --advantage gae --adv_norm --objective ppo --ppo_epochs 4 --ppo_minibatches 4 ...   # + PPO's clipped surrogate, 16 steps per round
     python -m mfrl_amd.train_battle --algo mfq --envs 64 --rollout --eval_every 10 --eval_oppo rush ...   # + a round against the scripted opponent, logged to data/eval_<algo>.jsonl
 
 Same arguments, epsilon schedule (linear_decay) and Runner as the reference; models from
@@ -18,6 +19,7 @@ mfrl_amd.algo (PyTorch-ROCm), the env from the drop-in magent (one env) or a Bat
 Logs go to data/tmp/<algo>.jsonl, models to data/models/<algo>-{0,1}/<algo>_<round>.pt.
 """
 import argparse
+import math
 import os
 import time
 
@@ -93,6 +95,19 @@ def main(argv=None):
                         help="with --advantage gae: lambda in [0, 1] (default 0.95)")
     parser.add_argument("--adv_norm", action="store_true",
                         help="with --advantage gae: normalise a round's advantages to zero mean and unit deviation")
+    parser.add_argument("--objective", type=str, choices=["pg", "ppo"], default="pg",
+                        help="ac / mfac with --rollout_episodes and --advantage gae: the policy term -- pg (the reference: "
+                             "one gradient and one Adam step per round) or ppo (the clipped surrogate, --ppo_epochs passes "
+                             "of --ppo_minibatches steps per round)")
+    parser.add_argument("--ppo_clip", type=float, default=None,
+                        help="with --objective ppo: the ratio's clip range, finite and > 0 (default 0.2)")
+    parser.add_argument("--ppo_epochs", type=int, default=None,
+                        help="with --objective ppo: passes over a round's rows, >= 1 (default 4)")
+    parser.add_argument("--ppo_minibatches", type=int, default=None,
+                        help="with --objective ppo: contiguous segments (Adam steps) per pass, >= 1 (default 4)")
+    parser.add_argument("--ppo_target_kl", type=float, default=None,
+                        help="with --objective ppo: start no further pass once a pass's mean approximate KL exceeds this "
+                             "(finite, >= 0; default: no such stop, and nothing read back inside the step loop)")
     parser.add_argument("--eval_every", type=int, default=0,
                         help="after every K-th round play one evaluation round of the main model against a scripted "
                              "opponent on the device rollout loop and log the outcome (0: off)")
@@ -141,6 +156,27 @@ def main(argv=None):
             parser.error("--gae_lambda must be in [0, 1]")
     if args.adv_norm and args.advantage != "gae":
         parser.error("--adv_norm normalises the advantages of --advantage gae: give that too")
+    if args.objective != "pg":
+        if args.algo not in ("ac", "mfac"):
+            parser.error("--objective ppo is the policy term of an actor-critic model: --algo ac or mfac (mfq / il train "
+                         "on their Q targets)")
+        if not args.rollout_episodes:
+            parser.error("--objective ppo runs on the device rollout loop: give --rollout_episodes")
+        if args.advantage != "gae":
+            parser.error("--objective ppo reads the advantage column of --advantage gae: give that too")
+    ppo_flags = {"--ppo_clip": args.ppo_clip, "--ppo_epochs": args.ppo_epochs, "--ppo_minibatches": args.ppo_minibatches,
+                 "--ppo_target_kl": args.ppo_target_kl}
+    for flag, value in ppo_flags.items():
+        if value is not None and args.objective != "ppo":
+            parser.error("%s describes --objective ppo: give that too" % flag)
+    if args.ppo_clip is not None and not (math.isfinite(args.ppo_clip) and args.ppo_clip > 0.0):
+        parser.error("--ppo_clip must be finite and > 0")
+    if args.ppo_epochs is not None and args.ppo_epochs < 1:
+        parser.error("--ppo_epochs must be >= 1")
+    if args.ppo_minibatches is not None and args.ppo_minibatches < 1:
+        parser.error("--ppo_minibatches must be >= 1")
+    if args.ppo_target_kl is not None and not (math.isfinite(args.ppo_target_kl) and args.ppo_target_kl >= 0.0):
+        parser.error("--ppo_target_kl must be finite and >= 0")
     if args.target != "max" and args.algo not in ("mfq", "il"):
         parser.error("--target boltzmann bootstraps from the Q values: --algo mfq or il (ac / mfac train on their "
                      "returns)")
@@ -209,6 +245,11 @@ def main(argv=None):
                 m.gae_lambda = args.gae_lambda
             if args.adv_norm:
                 m.adv_norm = True
+        if args.objective != "pg":
+            m.objective = args.objective
+            for name in ("ppo_clip", "ppo_epochs", "ppo_minibatches", "ppo_target_kl"):
+                if getattr(args, name) is not None:
+                    setattr(m, name, getattr(args, name))
     play_handle = play
     if args.envs > 1:
         from .battle import BattleBatch
